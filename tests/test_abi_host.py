@@ -51,7 +51,8 @@ def _potential(path, elem):
     return p
 
 
-@pytest.mark.parametrize("path,elem", [(FE_POT, "Fe"), (NI_POT, "Ni")])
+# (ids given by hand: the default ones would carry the absolute path of the checkout, another name for the same test in every directory)
+@pytest.mark.parametrize("path,elem", [(FE_POT, "Fe"), (NI_POT, "Ni")], ids=["fe_annp_potential_2.ann-Fe", "ni_annp_potential_2.ann-Ni"])
 def test_parser_matches_oracle_parser(path, elem):
     p = _potential(path, elem)
     q, o = p.potential(), read_pot(path)

@@ -85,3 +85,42 @@ def test_a_wire_that_hangs_ends_the_run_by_itself():
     assert r.returncode != 0
     assert "did not complete within" in r.stderr
     assert time.time() - t0 < 120
+
+
+def test_dump_outputs_rows_follow_the_atom_ids_whatever_the_rank_count(tmp_path):
+    """--dump-outputs: one row per atom in global id order, so that the files of two runs can be compared entry by entry even
+    when the atoms are spread over the ranks differently.  (Rehearsal: there is no force evaluation, so nothing moves and the
+    positions must be the generated ones, wrapped into the box.)"""
+    import numpy as np
+    from annp_testlib import A_FE, bcc, perturb
+    x0, box = bcc(12, 12, 12, A_FE)
+    x0, L = perturb(x0, 12345, 0.05), box[3:] - box[:3]
+    for gpus in (1, 2):
+        d = tmp_path / ("ranks%d" % gpus)
+        r = run_bench("--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--cells", "12", "--rebuild-every", "1", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len([l for l in r.stdout.splitlines() if l.strip()]) == 1, r.stdout
+        assert sorted(os.listdir(d)) == ["energy.npy", "forces.npy", "positions.npy", "velocities.npy"]
+        a = {n: np.load(d / (n + ".npy")) for n in ("energy", "forces", "positions", "velocities")}
+        assert all(v.dtype == np.float64 for v in a.values())
+        assert a["energy"].shape == (1,) and all(a[n].shape == x0.shape for n in ("forces", "positions", "velocities"))
+        dx = a["positions"] - x0
+        assert np.abs(dx - np.round(dx / L) * L).max() < 1e-12
+        assert not a["forces"].any() and not a["velocities"].any()
+
+
+def test_dump_outputs_of_a_large_box_is_a_fixed_sample_under_64_mb():
+    import numpy as np
+    import bench
+    assert np.array_equal(bench.dump_sample(2000), np.arange(2000))
+    n = 2 * 80 ** 3
+    keep = bench.dump_sample(n)
+    assert keep.size == bench.DUMP_MAX_ATOMS and 3 * keep.size * 3 * 8 + 8 + 4 * 128 <= 64e6        # three [n, 3] arrays, the energy, four .npy headers
+    assert np.all(np.diff(keep) > 0) and keep[0] >= 0 and keep[-1] < n
+    assert np.array_equal(keep, bench.dump_sample(n))
+    assert 0.95 < (keep < n // 2).sum() / (keep.size / 2) < 1.05                # drawn from the whole box, not its first atoms
+
+
+def test_zero_timed_steps_are_refused():
+    r = run_bench("--gpus", "1", "--steps", "0", "--cells", "6")
+    assert r.returncode == 2 and "--steps" in r.stderr and not r.stdout.strip()
