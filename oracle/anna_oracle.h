@@ -4,11 +4,12 @@
  * anna-gpu-lammps/bcc_fe/src/pair_anna_adp.cpp ("adp:" below).  Only tests/ may
  * call it; it is the checker, never the product.
  *
- * PARITY UNPINNED UPSTREAM: the reference ships neither tests nor a run log for
- * this pair style, and its translation unit needs LAMMPS core headers (absent),
- * so it cannot be built here.  The restatement is anchored on the reference's own
- * source (cited line by line) and on properties that must hold for it
- * (tests/test_anna_oracle.py): forces are the exact gradient of the energy with
+ * Parity pin: per-atom vectors of pair_anna_adp.cpp itself, compiled unmodified
+ * against oracle/ref_shim (tests/golden/ref_anna_golden.npz,
+ * tests/test_reference_vectors.py: eatom bit for bit, forces 6e-16, virial 2e-15).
+ * The reference ships neither tests nor a run log for this pair style.  The
+ * restatement cites the source line by line and is also checked for properties
+ * that must hold (tests/test_anna_oracle.py): forces are the exact gradient of the energy with
  * the two network outputs (d2, q2) held fixed -- which is what adp:231-279
  * differentiates -- total force zero, translation invariance.
  */

@@ -7,7 +7,10 @@
  * include/annp_hip.h and must fail loudly when that library is missing.
  *
  * Parity pin: the reference ships no tests.  This oracle is pinned
- * by (a) the reference's own published run log for its own data file
+ * by (0) per-atom vectors of the reference's own CPU pair styles, compiled
+ * unmodified against oracle/ref_shim (tests/golden/ref_annp_golden.npz,
+ * tests/test_reference_vectors.py: LITERAL bit for bit on Fe and on the first Ni
+ * call, 6e-14 otherwise), (a) the reference's own published run log for its own data file
  * (fe_v2 "performance test.zip": log_relaxing_new.lammps:118-120, step-0
  * E_pair / force norm / force max of fe_st.dat) and (b) the perfect-lattice
  * energies recorded in SURVEY.md Appendix B.  See tests/test_oracle_pins.py.

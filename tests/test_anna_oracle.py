@@ -1,7 +1,7 @@
 """pair_style anna_adp: the CPU oracle's self-consistency.
 
-The reference ships no test, log or golden value for this pair style and cannot be built here, so its oracle is
-"parity unpinned" upstream (oracle/anna_oracle.h).  What can be checked without the reference: the file is read
+The reference ships no test, log or golden value for this pair style; its oracle is pinned per atom to vectors of
+pair_anna_adp.cpp itself by tests/test_reference_vectors.py.  What is checked here, without the reference: the file is read
 as the reference's parser would read it, and the restated force loop (adp:215-280) is what it claims to be --
 the exact gradient of the restated energy (adp:165-212) with the two network outputs held fixed."""
 import numpy as np

@@ -1,6 +1,6 @@
-"""pair_style anna_adp on the HIP path against its CPU oracle.  The oracle is unpinned
-upstream (no reference test, log or buildable translation unit: oracle/anna_oracle.h); its own consistency is
-tests/test_anna_oracle.py."""
+"""pair_style anna_adp on the HIP path against its CPU oracle.  The oracle is pinned to
+vectors of pair_anna_adp.cpp itself (tests/test_reference_vectors.py), the HIP path as well
+(tests/test_gpu_reference_vectors.py); the oracle's own consistency is tests/test_anna_oracle.py."""
 import numpy as np
 import pytest
 
