@@ -103,92 +103,159 @@ class CopyPool {
     bool stop_ = false;
 };
 
-constexpr int ANNP_NFLAGS = 8;          // device flag words of an evaluation (annp_hip_handle::d_flags)
+namespace {
+
+// Device flag words of an evaluation.  FLAG_OVER is sticky: one word shared by every evaluation, set until the host has seen it.  The
+// others are per evaluation and come in two sets that take turns (EvalFlags).
+constexpr int ANNP_NFLAGS = 8;          // words per set (three are spare)
+enum FlagWord {
+    FLAG_OVER = 0,          // capacity error: max n of the atoms that were skipped (or ANNP_REPLAN_BAD_TARGET)
+    FLAG_NMAX = 1,          // max in-cutoff n
+    FLAG_NFIX_FORCE = 2,    // length of the force fix-up queue
+    FLAG_NFIX_DESC = 3,     // length of the descriptor fix-up queue
+    FLAG_SPILLS = 4,        // contributions annp_fe_force_sh's force tables had no bucket for
+};
+// the words of one evaluation as they landed on the host, and which evaluation that was (what digest_flags judges them by)
+struct FlagWords {
+    int over, mx, nfix_force, nfix_desc;
+    unsigned spills;        // (the device adds to an int: above 2^31 it reads negative)
+    bool sh;                // the evaluation ran the moment kernels
+    int inum;               // ... on that many atoms
+};
+
+// The flag words and everything that moves them: behind every evaluation a side stream copies its set to the host and clears it again
+// (hand_over), so no memset and no copy stands in the caller's stream between two evaluations, and an evaluation only waits for the
+// clearing of ITS set, two evaluations old (begin).  The host looks at a landed copy whenever it next touches the handle (poll).
+struct EvalFlags {
+    int *d_flags = nullptr;             // [3][ANNP_NFLAGS]: the sticky word's row and the two sets
+    int *h_flags = nullptr;             // pinned mirror of one evaluation's words, copied back behind every evaluation
+    int *fw = nullptr;                  // the set of the evaluation being issued (its words 1..7; word 0 is the sticky one of d_flags)
+    int par = 0;                        // ... which of the two that is
+    hipStream_t side = nullptr;         // the copy and the clearing run beside the caller's stream, not in it (at 128 000 atoms the copy held
+                                        // the next step's first kernel back by 33 us, the clearing cost two fill kernels)
+    hipEvent_t ev_tail = nullptr;       // the evaluation's last kernel is enqueued (what the side stream waits for)
+    hipEvent_t ev_landed = nullptr;     // the copy has landed
+    hipEvent_t ev_set[2] = {nullptr, nullptr};   // the side stream has cleared that set again
+    bool set_used[2] = {false, false};
+    bool dirty = false;                 // an evaluation set out and never reached hand_over (an error on the way): begin clears the words in-stream
+    bool pending = false;               // a copy into h_flags is in flight or not yet looked at
+    bool sh = false; int inum = 0;      // the evaluation the pending words belong to (FlagWords)
+    int sticky_rc = 0;                  // error found in a landed copy, returned by the next call on the handle
+    bool reset_err = false;             // the sticky word was seen non-zero: begin clears it
+
+    // device address of a word of the evaluation being issued (kernel arguments)
+    int *word(FlagWord w) const { return w == FLAG_OVER ? d_flags : fw + w; }
+    hipError_t allocate();
+    void release();
+    int begin(annp_hip_handle *h, hipStream_t s);
+    int read_now(annp_hip_handle *h, hipStream_t s, FlagWords &w);
+    int hand_over(annp_hip_handle *h, hipStream_t s, bool ran_sh, int ran_inum);
+    int settle(annp_hip_handle *h, bool wait);
+    int poll(annp_hip_handle *h, bool wait);
+
+   private:
+    int copy(annp_hip_handle *h, hipStream_t st);
+    FlagWords landed() const
+    {
+        return FlagWords{h_flags[FLAG_OVER], h_flags[FLAG_NMAX], h_flags[FLAG_NFIX_FORCE], h_flags[FLAG_NFIX_DESC], (unsigned)h_flags[FLAG_SPILLS], sh, inum};
+    }
+};
+
+}  // namespace
 
 struct annp_hip_handle {
     int device = 0;
     hipStream_t stream = nullptr;       // used by the host-pointer entry points
     std::string err;
-    // parameters (copied at init)
+    FILE *notice = nullptr;             // annp_hip_set_notice: where a change of kernel path is announced (once per change)
+    size_t bytes = 0;
+
+    // ---- the potential (copied at init) and the switches that go with its kernels (read_switches)
     int descriptor = 0, ntypes = 1, ntl = 0, nhl = 0, nnod = 0, nsf = 0, npsf = 0, ntsf = 0, nl = 0;
     int nsf_dev = 0;                    // features in the device layout (Chebyshev: always 9 + 19 slots, unused ones carry zero weights)
-    int ni_compat = 0;
-    bool ni_no_fixup = false;           // ANNP_HIP_NI_FIXUP=0: no queue behind the Behler records (overflow is an error again)
-    bool ni_no_pairs = false;           // ANNP_HIP_NI_PAIRS=0: the Behler force pass finds its pairs itself (no lists through memory)
-    bool full_list = false;             // ANNP_HIP_FULL_LIST=1: library-built lists are cut where the caller says (list_cutoff)
-    // pair_style anna_adp
-    int nout = 1;
-    double e_base = 0.0, gp[17] = {0};
-    double *d_net = nullptr;            // network image for annp_anna_adp (layer 0 in the device feature layout)
-    int net_doubles = 0;
-    int ni_cap = 24;                    // Behler kernels: record capacity per atom for the next evaluation
-    bool ni_primed = false;             // ... has been sized from a completed evaluation (else the next one sizes it synchronously)
-    int fe_cap = 0;                     // Chebyshev force pass: record capacity for the next evaluation (0 = not sized yet)
-    int cap_last = 0;                   // capacity the last force pass ran with
-    int sh_cap = 128;                   // Chebyshev descriptor pass (annp_fe_desc_sh): state slots per atom for the next evaluation.  The first one gets 128, not
-                                        // SH_CAP_MAX: up to there the pass keeps three workgroups per CU (160: two), and whoever has more goes through the fix-up launch once
-    bool fe_desc_pairs = false;         // ANNP_HIP_FE_DESC=pairs: the pair-loop descriptor kernel (annp_fe_desc) for every atom
-    bool fe_force_pairs = false;        // ANNP_HIP_FE_FORCE=pairs: the pair-loop force kernel (annp_fe_force) for every atom
-    int shf_places_by_number = 0;       // ANNP_HIP_SHF_PLACES=number: the one-slot wave of a group is its fourth wave, wherever it sits (developer A/B switch)
-    FILE *notice = nullptr;             // annp_hip_set_notice: where a change of kernel path is announced (once per change)
-    bool fe_dense_said = false;
-    int sh_cap_used = 0;                // state slots the last annp_fe_desc_sh launch had (= atoms with moments have at most that many neighbours)
-    bool fe_dense = false;              // most atoms have more neighbours than the moment kernels take (SH_CAP_MAX = 160): the pair-loop kernels for all
-    bool fe_last_sh = false;            // the last Chebyshev evaluation ran the moment kernels
-    bool flags_sh = false; int flags_inum = 0;      // ... and the evaluation the pending flag words belong to (several can be in flight)
-    bool shf_scattered = false, shf_scattered_said = false;       // the caller's atoms are in no spatial order (annp_fe_force_sh's force table)
-    int fe_last_inum = 0;
-    int sh_wpb = 0;                     // waves per workgroup of annp_fe_desc_sh (ANNP_HIP_SH_WPB; 0 = chosen per launch)
-    bool rp_images_by_dimension = false;    // ANNP_HIP_REPLAN_IMAGES=dims: annp_hip_replan_images waits for every dimension's count (rounds 4-5; A/B switch)
-    bool sh_group = false;              // ANNP_HIP_SH_TAIL=group: the descriptor pass changes basis group by group out of LDS where it can (round 6, measured 2 % slower; developer A/B switch)
     int flagact[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // up to max(MLP_MAXL, ANNA_MAXL) weight layers
     static_assert(MLP_MAXL <= 8 && ANNA_MAXL <= 8, "flagact holds 8 layers");
     double e_scale = 0, e_shift = 0, e_atom = 0, cut = 0, cutsq = 0;
     double *d_norm = nullptr;           // nmul | nsub | nden, ANNP_GPAD each
     double *d_mlp_img = nullptr;        // network pass: MFMA operand images (weights, biases, coefmat), one per element, mlp_build_image
     size_t img_stride = 0;              // doubles per element image
+    bool mlp_attr_done = false;
+    int mlp_blocks_per_cu = 0;          // resident workgroups of the network kernel per CU (occupancy query, once)
     int nelem = 1;
     bool multi = false;                 // several elements or an unmapped type: the kernels need atom types
     unsigned active = ~0u;              // bit t: type t is mapped to an element
     int *d_map = nullptr;               // device copy of map[0..ntypes]
-    double *d_sym = nullptr;            // BEHLER: function tables (ni_kernels.hpp, "per-function tables")
+    // Chebyshev
+    bool fe_desc_pairs = false;         // ANNP_HIP_FE_DESC=pairs: the pair-loop descriptor kernel (annp_fe_desc) for every atom
+    bool fe_force_pairs = false;        // ANNP_HIP_FE_FORCE=pairs: the pair-loop force kernel (annp_fe_force) for every atom
+    int shf_places_by_number = 0;       // ANNP_HIP_SHF_PLACES=number: the one-slot wave of a group is its fourth wave, wherever it sits (developer A/B switch)
+    bool virial_tally = false;          // ANNP_HIP_VIRIAL=tally: the pairwise tally inside the force kernels instead of sum x (x) f (what per-atom virials always use)
+    // Behler
+    int ni_compat = 0;
+    bool ni_no_fixup = false;           // ANNP_HIP_NI_FIXUP=0: no queue behind the Behler records (overflow is an error again)
+    bool ni_no_pairs = false;           // ANNP_HIP_NI_PAIRS=0: the Behler force pass finds its pairs itself (no lists through memory)
+    double *d_sym = nullptr;            // function tables (ni_kernels.hpp, "per-function tables")
     int *d_isym = nullptr;
     unsigned long long ni_rad_em = 0;   // NiArgs::rad_em
     NiShape ni_shape = {0, 0, 0};       // {lambda} x {eta} x {zeta} product shape of the angular set (0 = none)
     double ni_lam[4] = {0, 0, 0, 0}, ni_eta[4] = {0, 0, 0, 0};   // its distinct lambda / eta values in visit order
     std::vector<double> sym_rad, sym_ang;
-    // work buffers
+    // pair_style anna_adp
+    int nout = 1;
+    double e_base = 0.0, gp[17] = {0};
+    double *d_net = nullptr;            // network image for annp_anna_adp (layer 0 in the device feature layout)
+    int net_doubles = 0;
+
+    // ---- capacities and kernel paths learned from the evaluations before (digest_flags)
+    int ni_cap = 24;                    // Behler kernels: record capacity per atom for the next evaluation
+    bool ni_primed = false;             // ... has been sized from a completed evaluation (else the next one sizes it synchronously)
+    int fe_cap = 0;                     // Chebyshev pair-loop force pass: record capacity for the next evaluation (0 = not sized yet)
+    int cap_last = 0;                   // capacity the last force pass ran with
+    int sh_cap = 128;                   // Chebyshev descriptor pass (annp_fe_desc_sh): state slots per atom for the next evaluation.  The first one gets 128, not
+                                        // SH_CAP_MAX: up to there the pass keeps three workgroups per CU (160: two), and whoever has more goes through the fix-up launch once
+    int sh_cap_used = 0;                // state slots the last annp_fe_desc_sh launch had (= atoms with moments have at most that many neighbours)
+    bool fe_dense = false;              // most atoms have more neighbours than the moment kernels take (SH_CAP_MAX = 160): the pair-loop kernels for all
+    bool fe_dense_said = false;
+    bool shf_scattered = false, shf_scattered_said = false;       // the caller's atoms are in no spatial order (annp_fe_force_sh's force table)
+    int info[4] = {0, 0, 0, 0};         // annp_hip_eval_info
+
+    // ---- flag words of the evaluations
+    EvalFlags flags;
+
+    // ---- work buffers of an evaluation
+    DevBuf<double> G, coef, mom;        // mom: moments of the neighbourhoods, descriptor pass -> force pass (fe_sh_kernels.hpp)
     DevBuf<double> fscratch;            // forces of one evaluation by themselves, when the global virial is taken as sum x (x) f (annp_fdotr_add)
-    bool virial_tally = false;          // ANNP_HIP_VIRIAL=tally: the pairwise tally inside the force kernels instead (what per-atom virials always use)
-    DevBuf<double> G, coef, x, f, eatom, vatom, mom;        // mom: moments of the neighbourhoods, descriptor pass -> force pass (fe_sh_kernels.hpp)
-    DevBuf<int> type, ilist, numneigh, neigh, ncount, ni_nbr, ni_npair, ni_fix_nbr, ovf, ovf_desc, fe_nbrs;
+    DevBuf<int> ncount, ni_nbr, ni_npair, ni_fix_nbr, ovf, ovf_desc, fe_nbrs;
     DevBuf<unsigned short> ni_pairs;    // Behler: in-range (j,k) pairs per atom, descriptor pass -> force pass
-    DevBuf<long long> first;
-    // re-planning (replan_kernels.hpp): flags / scan positions / block sums of its stream compactions, their totals
+    double *d_vslots = nullptr;         // [ANNP_VSLOTS][8]: where the kernels tally the global virial (annp_common.hpp), folded per evaluation
+    hipEvent_t pre_force_wait = nullptr;    // set by the host path: the force pass must not start before this event
+    NeighBuild nb;                      // neighbour list built on the device
+
+    // ---- timing ring
+    bool timing = false;
+    static constexpr int kRing = 64;      // evaluations kept for annp_hip_timing_stats
+    std::vector<hipEvent_t> evring;       // kRing x 4 events, created on first enable
+    hipEvent_t *ev = nullptr;             // the four events of the evaluation being enqueued
+    long long ev_count = 0;               // evaluations recorded since timing was enabled
+
+    // ---- the halo wire (annp_hip_comm_*): one RCCL rank per handle
+    ncclComm_t comm = nullptr;
+    int comm_world = 0, comm_rank = -1;
+
+    // ---- re-planning (replan_kernels.hpp): flags / scan positions / block sums of its stream compactions, their totals
     DevBuf<int> rp_flag, rp_cnt;
     DevBuf<long long> rp_pos, rp_bs;
     long long *rp_tot = nullptr, *rp_tot_h = nullptr;
-    double *d_vslots = nullptr;         // [ANNP_VSLOTS][8]: where the kernels tally the global virial (annp_common.hpp), folded per evaluation
+
+    // ---- the host-pointer entry points: device copies of the caller's arrays and of its list
+    DevBuf<double> x, f, eatom, vatom;
+    DevBuf<int> type, ilist, numneigh, neigh;
+    DevBuf<long long> first;
     double *d_scalars = nullptr;        // [0] energy, [1..6] virial
-    int *d_flags = nullptr;             // [0] capacity error: max n of the atoms that were skipped (stays set until the host has
-                                        //     seen it), [1] max in-cutoff n, [2] length of the force fix-up queue, [3] of the descriptor fix-up queue,
-                                        //     [4] contributions annp_fe_force_sh's force tables had no bucket for; [1..] per evaluation
-    int *h_flags = nullptr;             // pinned mirror, copied back behind every evaluation
-    hipEvent_t ev_flags = nullptr;      // ... that copy has landed (and, behind it on the same side stream, words [1..] are clear again)
-    hipStream_t stream_flags = nullptr; // the copy and the clearing run beside the caller's stream, not in it (round 5: at 128 000 atoms the
-    hipEvent_t ev_tail = nullptr;       // copy held the next step's first kernel back by 33 us, the clearing cost two fill kernels)
-    int *fw = nullptr;                  // the per-evaluation words of the evaluation being issued: d_flags + 8 or + 16, turn about (fw[1..7]; word 0 of
-    int flags_par = 0;                  // d_flags is the sticky one) -- an evaluation never waits for the copy + clear behind the one before it
-    hipEvent_t ev_set[2] = {nullptr, nullptr};   // the side stream has cleared that set again
-    bool set_used[2] = {false, false};
-    bool flags_dirty = false;           // an evaluation set out and never reached its tail (an error on the way): clear the words in-stream
-    int sticky_rc = 0;                  // error found in a landed copy, returned by the next call on the handle
-    bool reset_err = false;             // d_flags[0] was seen non-zero: clear it before the next evaluation
-    int info[4] = {0, 0, 0, 0};         // annp_hip_eval_info
     double *h_scalars = nullptr;        // pinned mirror
-    // neighbour list built on device
-    NeighBuild nb;
-    // host-list cache
+    hipStream_t stream2 = nullptr;      // uploads that overlap the first passes of an evaluation
+    hipEvent_t ev_f_up = nullptr;       // the caller's f has arrived (pre_force_wait)
+    bool full_list = false;             // ANNP_HIP_FULL_LIST=1: library-built lists are cut where the caller says (list_cutoff)
     // pinned, persistent staging for what host_finish brings back (a fresh pageable vector per call costs its
     // page faults and a second copy inside the runtime: ~3 ms per 1 M atoms)
     double *pin_f = nullptr, *pin_e = nullptr, *pin_v = nullptr, *pin_x = nullptr;
@@ -197,12 +264,6 @@ struct annp_hip_handle {
     struct HostReg { const void *ptr = nullptr; size_t bytes = 0; bool ok = false; };
     HostReg reg_x, reg_f;
     bool use_register = true;           // ANNP_HIP_REGISTER=0 turns it off (pinned staging + host folds instead)
-    hipStream_t stream2 = nullptr;      // uploads that overlap the first passes of an evaluation
-    // RCCL communicator for the halo wire (annp_hip_comm_*): one rank per handle
-    ncclComm_t comm = nullptr;
-    int comm_world = 0, comm_rank = -1;
-    hipEvent_t ev_f_up = nullptr;
-    hipEvent_t pre_force_wait = nullptr;    // set by the host path: the force pass must not start before this event
     // host-list upload (annp_hip_compute, ago == 0): CSR headers and the rows go through pinned staging; the rows in
     // chunks, packed by a few threads while the previous chunk is on the wire
     long long *pin_first = nullptr;
@@ -211,7 +272,7 @@ struct annp_hip_handle {
     static constexpr int kListBufs = 3;
     static constexpr int kListParts = 8;        // runs of chunks a host list is evaluated in while it is uploaded (annp_hip_compute, ago == 0)
     hipEvent_t ev_part[kListParts] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int list_parts = 4;                         // ANNP_HIP_LIST_PARTS (1 = upload first, evaluate afterwards: rounds 1-5)
+    int list_parts = 4;                         // ANNP_HIP_LIST_PARTS (1 = upload first, evaluate afterwards)
     int list_pipe_min = 1 << 16;                // ... for lists of at least that many atoms (ANNP_HIP_LIST_PIPE_MIN)
     size_t list_chunk = kListChunk;             // ints per chunk of the upload (ANNP_HIP_LIST_CHUNK: smaller chunks let a test cut a small list into runs)
     static constexpr size_t kListChunk = (size_t)8 << 20;      // ints per staging buffer (32 MB)
@@ -220,16 +281,6 @@ struct annp_hip_handle {
     CopyPool *pool = nullptr;
     int list_max = 0;                   // max numneigh of the uploaded list
     bool list_valid = false;
-    size_t bytes = 0;
-    // timing
-    bool timing = false;
-    static constexpr int kRing = 64;      // evaluations kept for annp_hip_timing_stats
-    std::vector<hipEvent_t> evring;       // kRing x 4 events, created on first enable
-    hipEvent_t *ev = nullptr;             // the four events of the evaluation being enqueued
-    long long ev_count = 0;               // evaluations recorded since timing was enabled
-    bool flags_pending = false;         // a copy of d_flags into h_flags is in flight or not yet looked at
-    bool mlp_attr_done = false;
-    int mlp_blocks_per_cu = 0;          // resident workgroups of the network kernel per CU (occupancy query, once)
 };
 
 namespace {
@@ -370,13 +421,13 @@ int ni_next_cap(int mx) { return std::max(8, round_up(mx + std::max(2, mx / 8), 
 
 // Look at the flag words an evaluation copied back.  Updates the capacities for the next evaluation and turns a
 // device-side capacity error into sticky_rc.
-void digest_flags(annp_hip_handle *h)
+void digest_flags(annp_hip_handle *h, const FlagWords &w)
 {
-    int over = h->h_flags[0];
-    const int mx = h->h_flags[1], nfix = h->h_flags[2];
+    int over = w.over;
+    const int mx = w.mx, nfix = w.nfix_force;
     h->info[0] = mx; h->info[1] = nfix; h->info[2] = h->cap_last;
     if (over >= ANNP_REPLAN_BAD_TARGET) {        // not a neighbour count: annp_hip_replan_fold_plan was handed a target outside [0, nkeys)
-        h->sticky_rc = fail(h, ANNP_HIP_EARG, "replan_fold_plan: a target index lay outside [0, nkeys); it was left out of the plan");
+        h->flags.sticky_rc = fail(h, ANNP_HIP_EARG, "replan_fold_plan: a target index lay outside [0, nkeys); it was left out of the plan");
         over = 0;
     }
     if (mx > 0) h->sh_cap = sh_next_cap(mx);
@@ -385,7 +436,7 @@ void digest_flags(annp_hip_handle *h)
         // The moment kernels take atoms with up to SH_CAP_MAX neighbours and queue the others for the pair-loop fix-up launches, which
         // run one wave per workgroup: fine for a few atoms, slow for a dense system.  When a sixteenth of the atoms went through
         // the queue, the next evaluation uses the pair-loop kernels for all of them, until the maximum is back under the limit.
-        if (h->flags_sh) h->fe_dense = mx > SH_CAP_MAX && nfix > h->flags_inum / 16;
+        if (w.sh) h->fe_dense = mx > SH_CAP_MAX && nfix > w.inum / 16;
         else h->fe_dense = mx > SH_CAP_MAX;
         if (h->fe_dense != h->fe_dense_said) {          // a 2x change of speed the caller would otherwise only see in its timings
             h->fe_dense_said = h->fe_dense;
@@ -402,20 +453,20 @@ void digest_flags(annp_hip_handle *h)
         h->info[3] = (h->fe_dense || h->fe_desc_pairs || h->fe_force_pairs) ? h->fe_cap : h->sh_cap;     // capacity of the next force pass
         // The force table of annp_fe_force_sh keeps eight atoms with consecutive indices per bucket, and counts the contributions that
         // found none (each is three memory requests, where a bucket leaves with three for all its contributions).  Measured at 1 M
-        // atoms (round 5, tools/kbench.py): atoms in the order LAMMPS' atom_modify sort leaves them (bins of half the neighbour
+        // atoms (tools/kbench.py): atoms in the order LAMMPS' atom_modify sort leaves them (bins of half the neighbour
         // cutoff, no order inside a bin) lose 12.8 contributions per atom that way and the pass 4 % (5.45 -> 5.67 ms); atoms in
         // random order lose ~100 per atom and the pass takes 2.3 times as long.  The caller is told from 40 per atom on -- a third
         // of a bcc-Fe neighbourhood: sorting its atoms in space then buys up to that factor.
-        if (h->flags_sh) {
-            const long long lost = (long long)(unsigned)h->h_flags[4];        // (the device adds to an int: above 2^31 it reads negative)
-            h->shf_scattered = lost > 40 * (long long)h->flags_inum;
+        if (w.sh) {
+            const long long lost = (long long)w.spills;
+            h->shf_scattered = lost > 40 * (long long)w.inum;
             if (h->shf_scattered != h->shf_scattered_said) {
                 h->shf_scattered_said = h->shf_scattered;
                 if (h->notice) {
                     if (h->shf_scattered)
                         std::fprintf(h->notice, "annp/hip: atoms are not ordered in space (%.1f force contributions per atom found no room in the force pass's "
                                      "table of eight-atom buckets): the force pass takes up to 2.3 times as long as with sorted atoms (atom_modify sort)\n",
-                                     (double)lost / std::max(1, h->flags_inum));
+                                     (double)lost / std::max(1, w.inum));
                     else
                         std::fprintf(h->notice, "annp/hip: atoms are ordered in space again\n");
                     std::fflush(h->notice);
@@ -423,14 +474,14 @@ void digest_flags(annp_hip_handle *h)
             }
         }
         if (over > 0)
-            h->sticky_rc = fail(h, ANNP_HIP_ENEIGHCAP, "an atom has %d in-cutoff neighbours, more than the list-row capacity the "
-                                "evaluation was given (max_numneigh) or than LDS holds; it was skipped", over);
+            h->flags.sticky_rc = fail(h, ANNP_HIP_ENEIGHCAP, "an atom has %d in-cutoff neighbours, more than the list-row capacity the "
+                                      "evaluation was given (max_numneigh) or than LDS holds; it was skipped", over);
     } else if (h->descriptor == ANNP_HIP_DESC_BEHLER) {
         if (over > 0) {         // not an atom that outgrew its records (the fix-up launches take those): more than LDS can hold
             h->ni_cap = round_up(over + 2, 8);
             h->ni_primed = false;
-            h->sticky_rc = fail(h, ANNP_HIP_ENEIGHCAP, "%d neighbours inside the descriptor cutoff exceed what the kernels' LDS records can hold "
-                                "(or the list row is longer than max_numneigh said); the affected atoms were skipped", over);
+            h->flags.sticky_rc = fail(h, ANNP_HIP_ENEIGHCAP, "%d neighbours inside the descriptor cutoff exceed what the kernels' LDS records can hold "
+                                      "(or the list row is longer than max_numneigh said); the affected atoms were skipped", over);
         } else {
             h->ni_cap = ni_next_cap(mx);
         }
@@ -438,31 +489,114 @@ void digest_flags(annp_hip_handle *h)
     } else {
         h->info[3] = h->cap_last;
         if (over > 0)
-            h->sticky_rc = fail(h, ANNP_HIP_ENEIGHCAP, "%d neighbours inside the descriptor cutoff exceed the kernel capacity %d; "
-                                "the affected atoms were skipped", over, h->cap_last);
+            h->flags.sticky_rc = fail(h, ANNP_HIP_ENEIGHCAP, "%d neighbours inside the descriptor cutoff exceed the kernel capacity %d; "
+                                      "the affected atoms were skipped", over, h->cap_last);
     }
-    if (over > 0) h->reset_err = true;
+    if (over > 0) h->flags.reset_err = true;
 }
 
-// wait = false: only if the copy has landed already (never blocks); wait = true: block until it has.
-// Returns a pending error once.
-int poll_flags(annp_hip_handle *h, bool wait)
+// ---- EvalFlags ----------------------------------------------------------------------------------------------------------
+hipError_t EvalFlags::allocate()
 {
-    if (h->flags_pending) {
-        hipError_t e = wait ? hipEventSynchronize(h->ev_flags) : hipEventQuery(h->ev_flags);
-        if (e == hipSuccess) {
-            h->flags_pending = false;
-            digest_flags(h);
-        } else if (e != hipErrorNotReady) {
-            return fail(h, ANNP_HIP_EDEVICE, "flag read-back failed: %s", hipGetErrorString(e));
-        }
+    hipError_t e;
+    if ((e = hipMalloc((void **)&d_flags, 3 * ANNP_NFLAGS * sizeof(int))) != hipSuccess) return e;
+    if ((e = hipMemset(d_flags, 0, 3 * ANNP_NFLAGS * sizeof(int))) != hipSuccess) return e;
+    fw = d_flags + ANNP_NFLAGS;
+    for (hipEvent_t &ev : ev_set)
+        if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+    return hipHostMalloc((void **)&h_flags, ANNP_NFLAGS * sizeof(int));
+}
+
+void EvalFlags::release()
+{
+    if (d_flags) (void)hipFree(d_flags);
+    if (h_flags) (void)hipHostFree(h_flags);
+    if (ev_landed) (void)hipEventDestroy(ev_landed);
+    if (ev_tail) (void)hipEventDestroy(ev_tail);
+    for (hipEvent_t ev : ev_set) if (ev) (void)hipEventDestroy(ev);
+    if (side) (void)hipStreamDestroy(side);
+}
+
+// An evaluation sets out in stream s: its set of words is clear when its first kernel runs.
+int EvalFlags::begin(annp_hip_handle *h, hipStream_t s)
+{
+    if (dirty) {                // (the evaluation before this one left early: its set was never handed to the side stream)
+        HIP_TRY(h, hipMemsetAsync(fw + 1, 0, (ANNP_NFLAGS - 1) * sizeof(int), s));
+    } else {
+        par ^= 1;
+        fw = d_flags + ANNP_NFLAGS * (1 + par);
+        if (set_used[par]) HIP_TRY(h, hipStreamWaitEvent(s, ev_set[par], 0));      // cleared two evaluations ago
     }
-    if (h->sticky_rc) {
-        const int rc = h->sticky_rc;
-        h->sticky_rc = 0;
-        return rc;
+    dirty = true;
+    if (reset_err) {            // the sticky word, shared by both sets, once the host has seen it
+        HIP_TRY(h, hipMemsetAsync(d_flags, 0, sizeof(int), s));
+        reset_err = false;
     }
     return 0;
+}
+
+// the sticky word and the current evaluation's words into the host mirror
+int EvalFlags::copy(annp_hip_handle *h, hipStream_t st)
+{
+    HIP_TRY(h, hipMemcpyAsync(h_flags, d_flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(h_flags + 1, fw + 1, (ANNP_NFLAGS - 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// The words of the evaluation being issued as they stand behind what stream s holds so far: the synchronous sizing read of an
+// evaluation that has no capacity to go by (the first Chebyshev pair-loop evaluation, an un-primed Behler handle).
+int EvalFlags::read_now(annp_hip_handle *h, hipStream_t s, FlagWords &w)
+{
+    // One writer of the host mirror at a time: the copy of the evaluation before may still be on its way on the side stream -- landing
+    // late it would overwrite the words the host is about to read.  It is waited for and digested first (an error it carries is reported
+    // by the next look at the handle, as ever).
+    if (int rc = settle(h, true)) return rc;
+    if (int rc = copy(h, s)) return rc;
+    HIP_TRY(h, hipStreamSynchronize(s));
+    w = landed();
+    if (w.over > 0) reset_err = true;
+    return 0;
+}
+
+// The evaluation's last kernel is enqueued in s: its words are for whoever looks next (poll).
+int EvalFlags::hand_over(annp_hip_handle *h, hipStream_t s, bool ran_sh, int ran_inum)
+{
+    HIP_TRY(h, hipEventRecord(ev_tail, s));
+    HIP_TRY(h, hipStreamWaitEvent(side, ev_tail, 0));
+    // (a copy that is still pending is overwritten, not waited for: of the runs of a pipelined annp_hip_compute only the last one's words
+    // are digested.  Counting such a call as one evaluation for sizing purposes would be changed here and in the two fields below.)
+    if (int rc = copy(h, side)) return rc;
+    HIP_TRY(h, hipEventRecord(ev_landed, side));
+    HIP_TRY(h, hipMemsetAsync(fw + 1, 0, (ANNP_NFLAGS - 1) * sizeof(int), side));
+    HIP_TRY(h, hipEventRecord(ev_set[par], side));
+    set_used[par] = true;
+    pending = true; dirty = false;
+    sh = ran_sh; inum = ran_inum;
+    return 0;
+}
+
+// Look at a pending copy and digest it.  wait = false: only if it has landed already (never blocks); wait = true: block until it has.
+// (an error the words carry stays in sticky_rc for poll)
+int EvalFlags::settle(annp_hip_handle *h, bool wait)
+{
+    if (!pending) return 0;
+    const hipError_t e = wait ? hipEventSynchronize(ev_landed) : hipEventQuery(ev_landed);
+    if (e == hipSuccess) {
+        pending = false;
+        digest_flags(h, landed());
+    } else if (e != hipErrorNotReady) {
+        return fail(h, ANNP_HIP_EDEVICE, "flag read-back failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// settle, and return a pending error once
+int EvalFlags::poll(annp_hip_handle *h, bool wait)
+{
+    if (int rc = settle(h, wait)) return rc;
+    const int rc = sticky_rc;
+    sticky_rc = 0;
+    return rc;
 }
 
 // Cutoff of a neighbour list the library builds itself (annp_hip_neigh_build_device, annp_hip_compute_n) when the caller
@@ -501,15 +635,58 @@ struct DeviceGuard {
     DeviceGuard guard_((h)->device);                                                                 \
     if (guard_.err != hipSuccess) return fail(h, ANNP_HIP_EDEVICE, "hipSetDevice(%d) failed: %s", (h)->device, hipGetErrorString(guard_.err))
 
-// waves per workgroup of the Chebyshev passes (the kernels take any 1..4: waves never synchronise with each other).
-// Measured at 1 M atoms: force pass 14.63 ms with 4, 15.1 with 2, 14.9 with 1; descriptor pass indifferent.
-constexpr int fe_wpb_desc() { return ANNP_WAVES_PER_BLOCK; }
-constexpr int fe_wpb_force() { return ANNP_WAVES_PER_BLOCK; }
+// ---- one evaluation on device-resident data ----------------------------------------
+// Nothing here waits for the device in the steady state: capacities come from the previous evaluation's flag
+// words (whenever their copy has landed), this evaluation's flag words are copied back behind its last kernel.
+// Only the first evaluation on a handle (and the one after a Behler capacity error) sizes itself synchronously.
+
+// what an evaluation works on: the caller's device arrays, in the caller's stream
+struct EvalArgs {
+    int inum, nall, max_numneigh;
+    const double *x;
+    const int *types;           // null when the potential does not distinguish atom types
+    const int *ilist, *numneigh;
+    const long long *first;
+    const int *neigh;
+    double *f, *eatom, *eng;
+    double *vtab;               // where the kernels tally the global virial (null: none wanted, or taken from the forces afterwards)
+    double *vatom;
+    hipStream_t s;
+    int cap_list() const { return std::max(16, round_up(max_numneigh, 16)); }      // room for a whole list row
+    bool vir() const { return vtab || vatom; }
+};
+
+// timing event k of the evaluation being enqueued (0 opens its slot of the ring, 3 closes it)
+int record_timing(annp_hip_handle *h, int k, hipStream_t s)
+{
+    if (!h->timing) return 0;
+    if (k == 0) h->ev = h->evring.data() + 4 * (size_t)(h->ev_count % annp_hip_handle::kRing);
+    HIP_TRY(h, hipEventRecord(h->ev[k], s));
+    if (k == 3) h->ev_count++;
+    return 0;
+}
+
+// the force pass must not start before pre_force_wait (the host path's upload of the caller's f)
+int wait_pre_force(annp_hip_handle *h, hipStream_t s)
+{
+    if (h->pre_force_wait) { HIP_TRY(h, hipStreamWaitEvent(s, h->pre_force_wait, 0)); h->pre_force_wait = nullptr; }
+    return 0;
+}
+
+// the maximum of the counts a pair-loop descriptor pass left in ncount, into the evaluation's maximum word (annp_fe_desc_sh raises it itself)
+int launch_max_count(annp_hip_handle *h, int inum, hipStream_t s)
+{
+    hipLaunchKernelGGL(annp_max_int, dim3(annp_max_int_blocks(inum)), dim3(256), 0, s, h->ncount.p, inum, h->flags.word(FLAG_NMAX));
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
 
 template <bool VIR>
 void launch_fe_force(const FeArgs &a, hipStream_t s)
 {
-    const int wpb = fe_wpb_force();
+    // waves per workgroup of the pair-loop Chebyshev kernels (they take any 1..4: waves never synchronise with each other).
+    // Measured at 1 M atoms: force pass 14.63 ms with 4, 15.1 with 2, 14.9 with 1; descriptor pass indifferent.
+    const int wpb = ANNP_WAVES_PER_BLOCK;
     const int blocks = (a.inum + wpb - 1) / wpb;
     if (a.n_cap == 128)         // the capacity of a bcc-Fe box: layout offsets are compile-time constants
         hipLaunchKernelGGL((annp_fe_force<FE_NP, FE_NT, VIR, true, 128>), dim3(blocks), dim3(64 * wpb), fe_force_lds_per_wave(128, true) * wpb, s, a);
@@ -519,52 +696,69 @@ void launch_fe_force(const FeArgs &a, hipStream_t s)
         hipLaunchKernelGGL((annp_fe_force<FE_NP, FE_NT, VIR, false>), dim3(blocks), dim3(64 * wpb), fe_force_lds_per_wave(a.n_cap, false) * wpb, s, a);
 }
 
+// The pair-loop launch behind a Chebyshev force pass, for the atoms that pass queued: one wave per workgroup, room for a whole list row
+int launch_fe_force_fixup(annp_hip_handle *h, FeArgs b, int cap_list, bool vir, hipStream_t s)
+{
+    b.n_cap = cap_list;
+    const size_t lds_fix = fe_force_lds_per_wave(cap_list, false);
+    const int fblocks = std::min(b.inum, 1024);
+    if (vir) hipLaunchKernelGGL((annp_fe_force_fixup<FE_NP, FE_NT, true>), dim3(fblocks), dim3(64), lds_fix, s, b);
+    else hipLaunchKernelGGL((annp_fe_force_fixup<FE_NP, FE_NT, false>), dim3(fblocks), dim3(64), lds_fix, s, b);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+// What every kernel of the Chebyshev descriptor gets (pair_style annp Fe and anna_adp): the list, the cutoffs -- fc ends at rc_list, the
+// radial argument runs to the file's cutoff --, the descriptor rows and counts, the error and maximum words
+FeArgs fe_args(const annp_hip_handle *h, const EvalArgs &e, double rc_list)
+{
+    FeArgs a{};
+    a.inum = e.inum; a.ilist = e.ilist; a.x = e.x; a.numneigh = e.numneigh; a.first = e.first; a.neigh = e.neigh;
+    a.cutsq = h->cutsq; a.rc_list = rc_list; a.rc_par = h->cut;
+    a.por_list = ANNP_MY_PI / a.rc_list; a.two_over_rcp = 2.0 / a.rc_par;
+    a.G = h->G.p; a.ncount = h->ncount.p;
+    a.errflag = h->flags.word(FLAG_OVER);
+    a.nmax_word = h->flags.word(FLAG_NMAX);
+    return a;
+}
+
 // Chebyshev descriptor pass (pair_style annp Fe and anna_adp): the moment kernel for atoms with at most sh_cap in-cutoff
 // neighbours, the pair-loop kernel behind it for the ones it queued (none in the steady state: microseconds)
-int launch_fe_desc(annp_hip_handle *h, FeArgs a, int inum, int cap_list, int max_numneigh, hipStream_t s)
+int launch_fe_desc(annp_hip_handle *h, FeArgs a, const EvalArgs &e)
 {
     int rc;
-    if (h->fe_desc_pairs || (h->fe_dense && h->descriptor == ANNP_HIP_DESC_CHEBYSHEV)) {
+    const int inum = e.inum, cap_list = e.cap_list();
+    hipStream_t s = e.s;
+    if (h->fe_desc_pairs || (h->fe_dense && h->descriptor == ANNP_HIP_DESC_CHEBYSHEV)) {      // the pair-loop kernel for every atom
         a.n_cap = cap_list;
-        const int wpd = fe_wpb_desc();
+        const int wpd = ANNP_WAVES_PER_BLOCK;       // (launch_fe_force: indifferent here)
         const size_t lds1 = fe_desc_lds_per_wave(a.n_cap) * wpd;
-        if (lds1 > 160 * 1024) return fail(h, ANNP_HIP_ENEIGHCAP, "neighbour list too long for LDS (%d)", max_numneigh);
+        if (lds1 > 160 * 1024) return fail(h, ANNP_HIP_ENEIGHCAP, "neighbour list too long for LDS (%d)", e.max_numneigh);
         hipLaunchKernelGGL((annp_fe_desc<FE_NP, FE_NT>), dim3((inum + wpd - 1) / wpd), dim3(64 * wpd), lds1, s, a);
         HIP_TRY(h, hipGetLastError());
-        return 0;
+        return launch_max_count(h, inum, s);
     }
     const int cap = std::max((int)SH_CAP_MIN, std::min(h->sh_cap, cap_list));          // multiples of 16
     const size_t lds_fix = fe_desc_lds_per_wave(cap_list);
     const bool fix = cap_list > cap;
-    if (fix && lds_fix > 160 * 1024) return fail(h, ANNP_HIP_ENEIGHCAP, "neighbour list too long for LDS (%d)", max_numneigh);
+    if (fix && lds_fix > 160 * 1024) return fail(h, ANNP_HIP_ENEIGHCAP, "neighbour list too long for LDS (%d)", e.max_numneigh);
     if (fix && (rc = ensure(h, h->ovf_desc, (size_t)inum))) return rc;
     a.n_cap = cap;
     h->sh_cap_used = cap;
     if (!a.A) {         // the kernel sums monomial moments and changes basis in the atom's moment row: it needs one, whoever reads it afterwards
-        if ((rc = ensure(h, h->mom, (size_t)(inum + SHF_GA) * SH_MPAD, true))) return rc;      // (sized and zeroed as the force pass wants it, below)
+        if ((rc = ensure(h, h->mom, (size_t)(inum + SHF_GA) * SH_MPAD, true))) return rc;      // (sized and zeroed as the force pass wants it)
         a.A = h->mom.p;
     }
-    a.ovf_count = h->fw + 3; a.ovf_list = fix ? h->ovf_desc.p : nullptr; a.ovf_cap = fix ? inum : 0;
+    a.ovf_count = h->flags.word(FLAG_NFIX_DESC); a.ovf_list = fix ? h->ovf_desc.p : nullptr; a.ovf_cap = fix ? inum : 0;
     // waves per workgroup: as many waves per CU as the LDS allows, and of those shapes the largest workgroup (measured at
     // 1 M atoms, 8 waves per CU each: 5.8 ms with 4 waves per workgroup, 6.3 with 1)
-    int wpb = h->sh_wpb;
-    if (wpb <= 0) {
-        int best = 0;
-        for (int w = 1; w <= 4; w++) {
-            const int waves = (int)((size_t)160 * 1024 / (sh_lds_per_wave(cap) * w)) * w;
-            if (waves >= best) { best = waves; wpb = w; }
-        }
+    int wpb = 1;
+    for (int w = 1, best = 0; w <= 4; w++) {
+        const int waves = (int)((size_t)160 * 1024 / (sh_lds_per_wave(cap) * w)) * w;
+        if (waves >= best) { best = waves; wpb = w; }
     }
     const int groups = (inum + SH_GA - 1) / SH_GA;
-    // The monomial totals are parked in the moment row and changed of basis at the end (round 4b).  ANNP_HIP_SH_TAIL=group (developer A/B
-    // switch) selects round 6's variant for launches with room for at most 112 neighbours per atom: the change of basis group by group
-    // out of LDS, nothing parked -- 3 GB less memory traffic per 1 M-atom launch and 2 % SLOWER (4.84-4.86 against 4.72-4.77 ms on one box,
-    // alternating: gpurun_out/r6_ab2), as round 4's five-group version was: the pass does not wait for that traffic, and three tails in
-    // the middle of the columns cost more than one at the end.
-    if (cap <= SHG_CAP_MAX && h->sh_group)
-        hipLaunchKernelGGL((annp_fe_desc_sh<FE_NP, FE_NT, true>), dim3((groups + wpb - 1) / wpb), dim3(64 * wpb), sh_lds_per_wave(cap) * wpb, s, a);
-    else
-        hipLaunchKernelGGL((annp_fe_desc_sh<FE_NP, FE_NT, false>), dim3((groups + wpb - 1) / wpb), dim3(64 * wpb), sh_lds_per_wave(cap) * wpb, s, a);
+    hipLaunchKernelGGL((annp_fe_desc_sh<FE_NP, FE_NT>), dim3((groups + wpb - 1) / wpb), dim3(64 * wpb), sh_lds_per_wave(cap) * wpb, s, a);
     HIP_TRY(h, hipGetLastError());
     if (fix) {
         FeArgs b = a;
@@ -575,23 +769,191 @@ int launch_fe_desc(annp_hip_handle *h, FeArgs a, int inum, int cap_list, int max
     return 0;
 }
 
-// ---- one evaluation on device-resident data ----------------------------------------
-// Nothing here waits for the device in the steady state: capacities come from the previous evaluation's flag
-// words (whenever their copy has landed), this evaluation's flag words are copied back behind its last kernel.
-// Only the first evaluation on a handle (and the one after a Behler capacity error) sizes itself synchronously.
-// the sticky word and the current evaluation's words into the host mirror, in the layout digest_flags reads
-int copy_flags(annp_hip_handle *h, hipStream_t st)
+// Chebyshev force pass on the moments: atoms the descriptor pass had no state for (more than sh_cap_used neighbours) go to the queue
+// and the pair-loop fix-up launch, which has room for a whole list row; nothing to size, nothing to wait for
+int fe_force_on_moments(annp_hip_handle *h, FeArgs a, const EvalArgs &e)
 {
-    // One writer of the host mirror at a time: the synchronous sizing paths copy in the caller's stream while the copy of the
-    // evaluation before may still be on its way on the side stream -- landing late it would overwrite the words the host is about
-    // to read.  It is waited for and digested first (an error it carries is reported by the next look at the handle, as ever).
-    if (st != h->stream_flags && h->flags_pending) {
-        HIP_TRY(h, hipEventSynchronize(h->ev_flags));
-        h->flags_pending = false;
-        digest_flags(h);
+    int rc;
+    const int inum = e.inum, cap_list = e.cap_list(), cap = h->sh_cap_used;
+    const bool fixup = cap_list > cap;
+    if (fixup && (rc = ensure(h, h->ovf, (size_t)inum))) return rc;
+    a.n_cap = cap;
+    a.ovf_count = h->flags.word(FLAG_NFIX_FORCE); a.ovf_list = fixup ? h->ovf.p : nullptr; a.ovf_cap = fixup ? inum : 0;
+    if ((rc = wait_pre_force(h, e.s))) return rc;
+    a.tab_spills = h->flags.word(FLAG_SPILLS);
+    a.shf_places_by_number = h->shf_places_by_number;
+#ifdef ANNP_SHF_CHECK
+    a.chk_nall = e.nall;                        // (developer build: the kernel checks its indices against it)
+#endif
+    const int apb = SHF_GROUPS * SHF_GA;        // atoms per workgroup
+    if (e.vir()) hipLaunchKernelGGL((annp_fe_force_sh<FE_NP, FE_NT, true>), dim3((inum + apb - 1) / apb), dim3(64 * SHF_WAVES), shf_lds_per_block(), e.s, a);
+    else hipLaunchKernelGGL((annp_fe_force_sh<FE_NP, FE_NT, false>), dim3((inum + apb - 1) / apb), dim3(64 * SHF_WAVES), shf_lds_per_block(), e.s, a);
+    HIP_TRY(h, hipGetLastError());
+    if (fixup && (rc = launch_fe_force_fixup(h, a, cap_list, e.vir(), e.s))) return rc;
+    h->cap_last = cap;
+    return 0;
+}
+
+// Chebyshev force pass by pair loop (a dense system, ANNP_HIP_FE_FORCE=pairs, or no room for the fix-up launch): LDS records sized by the
+// in-cutoff maximum of the previous evaluation; an atom that has more is queued by the kernel and taken by the fix-up launch behind it
+int fe_force_by_pairs(annp_hip_handle *h, FeArgs a, const EvalArgs &e, bool fix_possible)
+{
+    int rc;
+    const int inum = e.inum, cap_list = e.cap_list();
+    int cap3;
+    // first evaluation on this handle: read the maximum just measured, once.  Also whenever a whole list row would not
+    // fit the fix-up launch's LDS (very long rows): nothing would stand behind a stale capacity then
+    if (h->fe_cap == 0 || (!fix_possible && h->fe_cap < cap_list)) {
+        FlagWords w;
+        if ((rc = h->flags.read_now(h, e.s, w))) return rc;
+        if (w.over > 0) return fail(h, ANNP_HIP_ENEIGHCAP, "in-cutoff neighbours %d exceed capacity %d", w.over, a.n_cap);
+        cap3 = std::max(16, round_up(w.mx, 16));
+        h->fe_cap = fe_next_cap(w.mx);
+    } else {
+        cap3 = std::min(h->fe_cap, cap_list);
     }
-    HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->d_flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(h->h_flags + 1, h->fw + 1, (ANNP_NFLAGS - 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+    if ((rc = ensure(h, h->ovf, (size_t)inum))) return rc;
+    a.n_cap = cap3;
+    const bool fixup = cap3 < cap_list && fix_possible;
+    a.ovf_count = h->flags.word(FLAG_NFIX_FORCE); a.ovf_list = fixup ? h->ovf.p : nullptr; a.ovf_cap = fixup ? inum : 0;
+    if (fe_force_lds_per_wave(cap3) * ANNP_WAVES_PER_BLOCK > 160 * 1024)
+        return fail(h, ANNP_HIP_ENEIGHCAP, "too many in-cutoff neighbours for LDS (%d)", cap3);
+    if ((rc = wait_pre_force(h, e.s))) return rc;
+    if (e.vir()) launch_fe_force<true>(a, e.s); else launch_fe_force<false>(a, e.s);
+    HIP_TRY(h, hipGetLastError());
+    if (fixup && (rc = launch_fe_force_fixup(h, a, cap_list, e.vir(), e.s))) return rc;
+    h->cap_last = cap3;
+    return 0;
+}
+
+// pair_style annp, Chebyshev descriptor: descriptor pass -> network pass -> force pass.  ran_sh: the moment kernels did it.
+int evaluate_chebyshev(annp_hip_handle *h, const EvalArgs &e, MlpArgs m, bool &ran_sh)
+{
+    int rc;
+    FeArgs a = fe_args(h, e, std::sqrt(h->cutsq));
+    a.type = e.types; a.active = h->active;
+    a.coef = h->coef.p; a.f = e.f; a.virial = e.vtab; a.vatom = e.vatom;
+    // pass 1 (and, for the force pass on the moments, their buffer; that pass needs the fix-up launch behind it)
+    const bool fix_possible = fe_force_lds_per_wave(e.cap_list(), false) <= 160 * 1024;     // the fix-up runs one wave per workgroup
+    const bool sh_force = !h->fe_desc_pairs && !h->fe_force_pairs && !h->fe_dense && fix_possible;
+    ran_sh = sh_force;
+    if (sh_force) {
+        // the moment rows start out as zeros: annp_fe_force_shp copies the rows of a unit's eight list entries into LDS as they are,
+        // the rows of atoms the descriptor pass left to the fix-up launch (never written, or written by an earlier evaluation)
+        // and up to SHF_GA rows behind the last entry included, and multiplies some of what it copied by zero
+        if ((rc = ensure(h, h->mom, (size_t)(e.inum + SHF_GA) * SH_MPAD, true)) || (rc = ensure(h, h->fe_nbrs, (size_t)e.inum * SH_CAP_MAX))) return rc;
+        a.A = h->mom.p; a.nbrs = h->fe_nbrs.p;
+    }
+    if ((rc = launch_fe_desc(h, a, e)) || (rc = record_timing(h, 1, e.s))) return rc;
+    // pass 2
+    m.act_plain = 0; m.energy_raw = 0;
+    if ((rc = run_mlp_elements(h, m, e.s)) || (rc = record_timing(h, 2, e.s))) return rc;
+    // pass 3
+    return sh_force ? fe_force_on_moments(h, a, e) : fe_force_by_pairs(h, a, e, fix_possible);
+}
+
+// pair_style anna_adp: the Chebyshev descriptor pass, then one kernel for network, ADP sums, energy and forces
+int evaluate_anna_adp(annp_hip_handle *h, const EvalArgs &e)
+{
+    int rc;
+    // pass 1: the same Chebyshev descriptor kernel, raw sums (adp:584-612 has no normalisation); fc and the radial argument both use
+    // the file's cutoff (adp:105,130,588)
+    const FeArgs a = fe_args(h, e, h->cut);
+    if ((rc = launch_fe_desc(h, a, e)) || (rc = record_timing(h, 1, e.s)) || (rc = record_timing(h, 2, e.s))) return rc;
+    // pass 2: network, ADP sums, energy, forces
+    AnnaArgs q{};
+    q.inum = e.inum; q.ilist = e.ilist; q.x = e.x; q.numneigh = e.numneigh; q.first = e.first; q.neigh = e.neigh;
+    q.n_cap = 64 * ANNA_NR; q.rc = h->cut; q.G = h->G.p; q.net = h->d_net;
+    q.net_doubles = h->net_doubles; q.net_in_lds = h->net_doubles <= ANNA_NET_LDS_MAX;
+    q.nl = h->nl; q.nin = h->nsf_dev; q.nnod = h->nnod; q.nout = h->nout;
+    for (int l = 0; l < h->nl; l++) q.actp |= (unsigned)(h->flagact[l] & 15) << (4 * l);
+    for (int k = 0; k < 17; k++) q.gp[k] = h->gp[k];
+    q.e_base = h->e_base;
+    q.f = e.f; q.eatom = e.eatom; q.eng = e.eng; q.virial = e.vtab; q.vatom = e.vatom; q.errflag = h->flags.word(FLAG_OVER);
+    const size_t lds2 = anna_lds_per_wave(q.n_cap) * ANNP_WAVES_PER_BLOCK + anna_lds_net(h->net_doubles);
+    if ((rc = wait_pre_force(h, e.s))) return rc;
+    if (e.vir()) hipLaunchKernelGGL((annp_anna_adp<true>), dim3(anna_blocks(e.inum)), dim3(256), lds2, e.s, q);
+    else hipLaunchKernelGGL((annp_anna_adp<false>), dim3(anna_blocks(e.inum)), dim3(256), lds2, e.s, q);
+    HIP_TRY(h, hipGetLastError());
+    // more in-range neighbours than a wave holds (128): the error word stays set on the device until the host
+    // has seen it, so it is reported by the next call or annp_hip_sync however many evaluations are enqueued
+    h->cap_last = q.n_cap;
+    return 0;
+}
+
+// pair_style annp, Behler descriptor: descriptor pass (+ fix-up) -> network pass -> force pass (+ fix-up)
+int evaluate_behler(annp_hip_handle *h, const EvalArgs &e, MlpArgs m)
+{
+    int rc;
+    const int inum = e.inum;
+    hipStream_t s = e.s;
+    NiArgs a{};
+    a.inum = inum; a.ilist = e.ilist; a.x = e.x; a.numneigh = e.numneigh; a.first = e.first; a.neigh = e.neigh;
+    a.npsf = h->npsf; a.ntsf = h->ntsf; a.sym = h->d_sym; a.isym = h->d_isym; a.compat = h->ni_compat;
+    a.type = e.types; a.active = h->active;
+    a.rc_rad = h->sym_rad[2]; a.rc_ang = h->sym_ang[3];
+    a.por_rad = ANNP_MY_PI / a.rc_rad; a.por_ang = ANNP_MY_PI / a.rc_ang;
+    a.rc2a = (a.rc_ang / ANNP_CFLENGTH) * (a.rc_ang / ANNP_CFLENGTH) * (1.0 + 1e-12);
+    for (int k = 0; k < 4; k++) { a.lam[k] = h->ni_lam[k]; a.eta[k] = h->ni_eta[k]; }
+    a.rad_em = h->ni_rad_em;
+    a.G = h->G.p; a.coef = h->coef.p; a.f = e.f; a.virial = e.vtab; a.vatom = e.vatom; a.ncount = h->ncount.p; a.errflag = h->flags.word(FLAG_OVER);
+    if (a.npsf > NI_MAXP || a.ntsf > NI_MAXT)
+        return fail(h, ANNP_HIP_ESHAPE, "Behler kernels support npsf<=%d ntsf<=%d", NI_MAXP, NI_MAXT);
+    const int cap_max = ni_max_cap(true, h->nsf);
+    // room for the pair lists the descriptor pass hands to the force pass: n_cap (n_cap - 1) / 2 entries of 2 bytes per
+    // atom (190 at capacity 20).  Not for very long records (the force pass then finds its pairs itself).
+    auto pair_room = [&](NiArgs &q) -> int {
+        q.pairs = nullptr; q.npair = nullptr; q.pstride = 0;
+        const long long ps = round_up(q.n_cap * (q.n_cap - 1) / 2, 8);
+        if (h->ni_no_pairs || ps > 2048 || (long long)inum * ps * 2 > (3ll << 30)) return 0;
+        int r;
+        if ((r = ensure(h, h->ni_pairs, (size_t)inum * ps)) || (r = ensure(h, h->ni_npair, (size_t)inum))) return r;
+        q.pairs = h->ni_pairs.p; q.npair = h->ni_npair.p; q.pstride = (int)ps;
+        return 0;
+    };
+    // Records: n_cap per atom from the previous evaluation's maximum.  A group of four atoms that has more is queued by the
+    // descriptor pass and taken, pass by pass, by a second small launch whose records hold a whole list row (cap_big), so
+    // the evaluation is complete whatever the configuration did since the capacity was learned.  An error remains only
+    // for more in-range neighbours than the largest records LDS can hold, or a list row longer than the caller said.
+    a.n_cap = std::min(h->ni_cap, cap_max);
+    if ((rc = ensure(h, h->ni_nbr, (size_t)inum * a.n_cap)) || (rc = pair_room(a))) return rc;
+    a.nbr = h->ni_nbr.p; a.nbr_stride = a.n_cap;
+    const int cap_big = std::min(cap_max, std::max(a.n_cap, round_up(std::max(e.max_numneigh, 8), 8)));
+    const bool fixup = cap_big > a.n_cap && !h->ni_no_fixup;
+    const int ngroups = (inum + NI_GA - 1) / NI_GA;
+    a.ovf_count = h->flags.word(FLAG_NFIX_FORCE); a.ovf_list = nullptr; a.ovf_cap = 0; a.fix = 0; a.skip_above = a.n_cap;
+    if (fixup) {
+        if ((rc = ensure(h, h->ovf, (size_t)ngroups)) || (rc = ensure(h, h->ni_fix_nbr, (size_t)ngroups * NI_GA * cap_big))) return rc;
+        a.ovf_list = h->ovf.p; a.ovf_cap = ngroups;
+    }
+    NiArgs b = a;           // the fix-up launches
+    b.fix = 1; b.n_cap = cap_big; b.nbr = h->ni_fix_nbr.p; b.nbr_stride = cap_big; b.pairs = nullptr; b.pstride = 0;
+    ni_launch_desc(a, h->ni_shape, s);
+    HIP_TRY(h, hipGetLastError());
+    if (fixup) { ni_launch_desc_fix(b, h->ni_shape, s); HIP_TRY(h, hipGetLastError()); }
+    if ((rc = launch_max_count(h, inum, s))) return rc;
+    int cap_force = a.n_cap;
+    if (!h->ni_primed) {    // first evaluation on the handle (or the one after an error): look at the counts once
+        FlagWords w;
+        if ((rc = h->flags.read_now(h, s, w))) return rc;
+        if (w.over > 0) {
+            h->ni_cap = std::min(cap_max, round_up(w.over + 2, 8));
+            return fail(h, ANNP_HIP_ENEIGHCAP, "%d neighbours inside the descriptor cutoff exceed the kernel capacity %d (list rows: %d)",
+                        w.over, cap_big, e.max_numneigh);
+        }
+        h->ni_cap = ni_next_cap(w.mx);
+        h->ni_primed = true;
+        cap_force = std::max(8, std::min(a.n_cap, round_up(w.mx, 2)));     // (fewer LDS bytes: more resident workgroups)
+    }
+    if ((rc = record_timing(h, 1, s))) return rc;
+    m.act_plain = 1; m.energy_raw = 1;
+    if ((rc = run_mlp_elements(h, m, s)) || (rc = record_timing(h, 2, s))) return rc;
+    a.n_cap = cap_force;
+    h->cap_last = cap_force;
+    if ((rc = wait_pre_force(h, s))) return rc;
+    ni_launch_force(a, h->ni_shape, e.vir(), s);
+    HIP_TRY(h, hipGetLastError());
+    if (fixup) { ni_launch_force_fix(b, h->ni_shape, e.vir(), s); HIP_TRY(h, hipGetLastError()); }
     return 0;
 }
 
@@ -600,10 +962,10 @@ int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_
                         double *d_f, double *d_eatom, double *d_eng, double *d_virial, double *d_vatom, hipStream_t s)
 {
     int rc;
-    if ((rc = poll_flags(h, false))) return rc;      // an error of an earlier evaluation, reported once
+    if ((rc = h->flags.poll(h, false))) return rc;      // an error of an earlier evaluation, reported once
     // A list build whose row maximum nobody has looked at yet (neigh_kernels.hpp: builds behind annp_hip_neigh_build_device do not wait
     // for it): looked at here as soon as the word has landed -- by the first or second evaluation on that list, never blocking -- so a
-    // row that outgrew the pitch is reported a step late, not a rebuild interval late (ADVICE r5)
+    // row that outgrew the pitch is reported a step late, not a rebuild interval late
     if (h->nb.pending && hipEventQuery(h->nb.ev_lazy) == hipSuccess) {
         std::string msg;
         if (int rs = neigh_settle(h->nb, msg)) return fail(h, rs, "%s", msg.c_str());
@@ -612,54 +974,34 @@ int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_
     // The global virial without per-atom virials (every step of an NPT run): the evaluation's forces go to a scratch array, and one
     // streaming kernel behind the passes adds them onto the caller's f and sums x (x) f over owned atoms and ghosts -- the reference's
     // own route (virial_fdotr_compute), equal to the pairwise tally to round-off, and 50 us where the tally cost the force pass 6 %.
-    double *f_caller = nullptr, *virial_caller = nullptr;
     // (Chebyshev potentials only: the reference's Behler file tallies its virial from the forces BEFORE their unit conversion
     // (ni/src/pair_annp.cpp:188-198: f gets Fj * CFFORCE, ev_tally_xyz gets Fj), so there the tally and sum x (x) f differ by that factor,
     // and the boundary's virial is the tally's; anna_adp keeps the tally too)
-    if (d_virial && !d_vatom && !h->virial_tally && h->descriptor == ANNP_HIP_DESC_CHEBYSHEV) {
+    const bool fdotr = d_virial && !d_vatom && !h->virial_tally && h->descriptor == ANNP_HIP_DESC_CHEBYSHEV;
+    if (fdotr) {
         if ((rc = ensure(h, h->fscratch, (size_t)nall * 3))) return rc;
         HIP_TRY(h, hipMemsetAsync(h->fscratch.p, 0, sizeof(double) * 3 * (size_t)nall, s));
-        f_caller = d_f; virial_caller = d_virial;
-        d_f = h->fscratch.p; d_virial = nullptr;
     }
     if ((rc = ensure(h, h->G, (size_t)inum * ANNP_GPAD))) return rc;
     // (coefficient rows start out as zeros, and there are rows behind the last list entry's: the force pass multiplies a few entries of
     // a neighbouring row by zero: they must be numbers, whether the network pass wrote them or not)
     if ((rc = ensure(h, h->coef, (size_t)(inum + SHF_GA) * ANNP_CPAD, true))) return rc;
     if ((rc = ensure(h, h->ncount, (size_t)inum))) return rc;
-    // The per-evaluation flag words come in two sets that take turns (h->fw): behind every evaluation a side stream copies its set to
-    // the host and clears it again (the tail of this function), so no memset and no copy stands in the caller's stream between two
-    // evaluations, and an evaluation only waits for the clearing of ITS set, two evaluations old.  Word [0] of d_flags is the sticky
-    // one, shared by both sets, cleared here once the host has seen it.
-    if (h->flags_dirty) {               // (the evaluation before this one left early: its set was never handed to the side stream)
-        HIP_TRY(h, hipMemsetAsync(h->fw + 1, 0, (ANNP_NFLAGS - 1) * sizeof(int), s));
-    } else {
-        h->flags_par ^= 1;
-        h->fw = h->d_flags + ANNP_NFLAGS * (1 + h->flags_par);
-        if (h->set_used[h->flags_par]) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_set[h->flags_par], 0));      // cleared two evaluations ago
-    }
-    h->flags_dirty = true;
-    if (h->reset_err) {
-        HIP_TRY(h, hipMemsetAsync(h->d_flags, 0, sizeof(int), s));
-        h->reset_err = false;
-    }
-    if (h->timing) {
-        h->ev = h->evring.data() + 4 * (size_t)(h->ev_count % annp_hip_handle::kRing);
-        HIP_TRY(h, hipEventRecord(h->ev[0], s));
-    }
+    if ((rc = h->flags.begin(h, s)) || (rc = record_timing(h, 0, s))) return rc;
 
-    const int cap_list = std::max(16, round_up(max_numneigh, 16));
-    double *vtab = nullptr;             // the global virial is tallied here and folded into d_virial at the end
-    if (d_virial) {
-        vtab = h->d_vslots;
-        HIP_TRY(h, hipMemsetAsync(vtab, 0, sizeof(double) * 8 * ANNP_VSLOTS, s));
+    EvalArgs e{};
+    e.inum = inum; e.nall = nall; e.max_numneigh = max_numneigh;
+    e.x = d_x; e.ilist = d_ilist; e.numneigh = d_numneigh; e.first = d_first; e.neigh = d_neigh;
+    e.f = fdotr ? h->fscratch.p : d_f; e.eatom = d_eatom; e.eng = d_eng; e.vatom = d_vatom; e.s = s;
+    if (d_virial && !fdotr) {           // the global virial is tallied here and folded into d_virial at the end
+        e.vtab = h->d_vslots;
+        HIP_TRY(h, hipMemsetAsync(e.vtab, 0, sizeof(double) * 8 * ANNP_VSLOTS, s));
     }
-
     if (h->multi && !d_type)
         return fail(h, ANNP_HIP_EARG, "this potential distinguishes atom types (several elements or an unmapped type): d_type is required");
-    const int *types = h->multi ? d_type : nullptr;
+    e.types = h->multi ? d_type : nullptr;
     MlpArgs m{};
-    m.type = types; m.map = h->d_map; m.elem = 0; m.active = h->active;
+    m.type = e.types; m.map = h->d_map; m.elem = 0; m.active = h->active;
     m.inum = inum; m.ilist = d_ilist; m.nsf = h->nsf_dev; m.nnod = h->nnod; m.nl = h->nl;
     m.ncoef = h->descriptor == ANNP_HIP_DESC_CHEBYSHEV ? FE_NP + 2 * FE_NT + 1 : h->nsf_dev;
     for (int l = 0; l < std::min(h->nl, (int)MLP_MAXL); l++) m.act[l] = h->flagact[l];      // (anna_adp may have more layers; it does not use m)
@@ -667,232 +1009,25 @@ int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_
     m.e_scale = h->e_scale; m.e_shift = h->e_shift; m.e_atom = h->e_atom;
     m.G = h->G.p; m.coef = h->coef.p; m.eatom = d_eatom; m.eng = d_eng;
 
-    if (h->descriptor == ANNP_HIP_DESC_CHEBYSHEV) {
-        FeArgs a{};
-        a.inum = inum; a.ilist = d_ilist; a.x = d_x; a.numneigh = d_numneigh; a.first = d_first; a.neigh = d_neigh;
-        a.cutsq = h->cutsq; a.rc_list = std::sqrt(h->cutsq); a.rc_par = h->cut;
-        a.por_list = ANNP_MY_PI / a.rc_list; a.two_over_rcp = 2.0 / a.rc_par;
-        a.type = types; a.active = h->active;
-        a.G = h->G.p; a.coef = h->coef.p; a.f = d_f; a.virial = vtab; a.vatom = d_vatom; a.ncount = h->ncount.p;
-        a.errflag = h->d_flags;
-        // pass 1 (and, for the force pass on the moments, their buffer; that pass needs the fix-up launch behind it)
-        const size_t lds_fix = fe_force_lds_per_wave(cap_list, false);      // the fix-up runs one wave per workgroup
-        const bool fix_possible = lds_fix <= 160 * 1024;
-        const bool sh_force = !h->fe_desc_pairs && !h->fe_force_pairs && !h->fe_dense && fix_possible;
-        h->fe_last_sh = sh_force; h->fe_last_inum = inum;
-        if (sh_force) {
-            // the moment rows start out as zeros: annp_fe_force_shp copies the rows of a unit's eight list entries into LDS as they are,
-            // the rows of atoms the descriptor pass left to the fix-up launch (never written, or written by an earlier evaluation)
-            // and up to SHF_GA rows behind the last entry included, and multiplies some of what it copied by zero
-            if ((rc = ensure(h, h->mom, (size_t)(inum + SHF_GA) * SH_MPAD, true)) || (rc = ensure(h, h->fe_nbrs, (size_t)inum * SH_CAP_MAX))) return rc;
-            a.A = h->mom.p; a.nbrs = h->fe_nbrs.p;
-        }
-        a.nmax_word = h->fw + 1;           // (annp_fe_desc_sh raises it itself; the pair-loop descriptor kernel does not)
-        const bool desc_sh = !h->fe_desc_pairs && !h->fe_dense;
-        if ((rc = launch_fe_desc(h, a, inum, cap_list, max_numneigh, s))) return rc;
-        if (!desc_sh) hipLaunchKernelGGL(annp_max_int, dim3(annp_max_int_blocks(inum)), dim3(256), 0, s, h->ncount.p, inum, h->fw + 1);
-        HIP_TRY(h, hipGetLastError());
-        if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[1], s));
-        // pass 2
-        m.act_plain = 0; m.energy_raw = 0;
-        if ((rc = run_mlp_elements(h, m, s))) return rc;
-        if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[2], s));
-        // pass 3: LDS records sized by the in-cutoff maximum of the previous evaluation; an atom that has more
-        // is queued by the kernel and taken by the fix-up launch behind it, which has room for a whole list row
-        const bool vir = d_virial || d_vatom;
-        if (sh_force) {
-            // pass 3 on the moments: atoms the descriptor pass had no state for (more than sh_cap_used neighbours) go to the queue
-            // and the pair-loop fix-up launch, which has room for a whole list row; nothing to size, nothing to wait for
-            const int cap = h->sh_cap_used;
-            const bool fixup = cap_list > cap;
-            if (fixup && (rc = ensure(h, h->ovf, (size_t)inum))) return rc;
-            a.n_cap = cap;
-            a.ovf_count = h->fw + 2; a.ovf_list = fixup ? h->ovf.p : nullptr; a.ovf_cap = fixup ? inum : 0;
-            if (h->pre_force_wait) { HIP_TRY(h, hipStreamWaitEvent(s, h->pre_force_wait, 0)); h->pre_force_wait = nullptr; }
-            a.tab_spills = h->fw + 4;
-            a.shf_places_by_number = h->shf_places_by_number;
-            {
-#ifdef ANNP_SHF_CHECK
-                a.chk_nall = nall;                          // (developer build: the kernel checks its indices against it)
-#endif
-                const int apb = SHF_GROUPS * SHF_GA;        // atoms per workgroup
-                if (vir) hipLaunchKernelGGL((annp_fe_force_sh<FE_NP, FE_NT, true>), dim3((inum + apb - 1) / apb), dim3(64 * SHF_WAVES), shf_lds_per_block(), s, a);
-                else hipLaunchKernelGGL((annp_fe_force_sh<FE_NP, FE_NT, false>), dim3((inum + apb - 1) / apb), dim3(64 * SHF_WAVES), shf_lds_per_block(), s, a);
-            }
-            HIP_TRY(h, hipGetLastError());
-            if (fixup) {
-                FeArgs b = a;
-                b.n_cap = cap_list;
-                const int fblocks = std::min(inum, 1024);
-                if (vir) hipLaunchKernelGGL((annp_fe_force_fixup<FE_NP, FE_NT, true>), dim3(fblocks), dim3(64), lds_fix, s, b);
-                else hipLaunchKernelGGL((annp_fe_force_fixup<FE_NP, FE_NT, false>), dim3(fblocks), dim3(64), lds_fix, s, b);
-                HIP_TRY(h, hipGetLastError());
-            }
-            h->cap_last = cap;
-        } else {        // the pair-loop force pass (rounds 1-2): a dense system, ANNP_HIP_FE_FORCE=pairs, or no room for the fix-up launch
-            int cap3;
-            // first evaluation on this handle: read the maximum just measured, once.  Also whenever a whole list row would not
-            // fit the fix-up launch's LDS (very long rows): nothing would stand behind a stale capacity then
-            if (h->fe_cap == 0 || (!fix_possible && h->fe_cap < cap_list)) {
-                if (int rc2 = copy_flags(h, s)) return rc2;
-                HIP_TRY(h, hipStreamSynchronize(s));
-                if (h->h_flags[0] > 0) {
-                    h->reset_err = true;
-                    return fail(h, ANNP_HIP_ENEIGHCAP, "in-cutoff neighbours %d exceed capacity %d", h->h_flags[0], a.n_cap);
-                }
-                cap3 = std::max(16, round_up(h->h_flags[1], 16));
-                h->fe_cap = fe_next_cap(h->h_flags[1]);
-            } else {
-                cap3 = std::min(h->fe_cap, cap_list);
-            }
-            if ((rc = ensure(h, h->ovf, (size_t)inum))) return rc;
-            a.n_cap = cap3;
-            const bool fixup = cap3 < cap_list && fix_possible;
-            a.ovf_count = h->fw + 2; a.ovf_list = fixup ? h->ovf.p : nullptr; a.ovf_cap = fixup ? inum : 0;
-            if (fe_force_lds_per_wave(cap3) * fe_wpb_force() > 160 * 1024)
-                return fail(h, ANNP_HIP_ENEIGHCAP, "too many in-cutoff neighbours for LDS (%d)", cap3);
-            if (h->pre_force_wait) { HIP_TRY(h, hipStreamWaitEvent(s, h->pre_force_wait, 0)); h->pre_force_wait = nullptr; }
-            if (vir) launch_fe_force<true>(a, s); else launch_fe_force<false>(a, s);
-            HIP_TRY(h, hipGetLastError());
-            if (fixup) {
-                FeArgs b = a;
-                b.n_cap = cap_list;
-                const int fblocks = std::min(inum, 1024);
-                if (vir) hipLaunchKernelGGL((annp_fe_force_fixup<FE_NP, FE_NT, true>), dim3(fblocks), dim3(64), lds_fix, s, b);
-                else hipLaunchKernelGGL((annp_fe_force_fixup<FE_NP, FE_NT, false>), dim3(fblocks), dim3(64), lds_fix, s, b);
-                HIP_TRY(h, hipGetLastError());
-            }
-            h->cap_last = cap3;
-        }
-    } else if (h->descriptor == ANNP_HIP_DESC_ANNA_ADP) {
-        // pass 1: the same Chebyshev descriptor kernel, raw sums (adp:584-612 has no normalisation)
-        FeArgs a{};
-        a.inum = inum; a.ilist = d_ilist; a.x = d_x; a.numneigh = d_numneigh; a.first = d_first; a.neigh = d_neigh;
-        a.cutsq = h->cutsq; a.rc_list = h->cut; a.rc_par = h->cut;          // fc and the radial argument both use the file's cutoff (adp:105,130,588)
-        a.por_list = ANNP_MY_PI / a.rc_list; a.two_over_rcp = 2.0 / a.rc_par;
-        a.G = h->G.p; a.ncount = h->ncount.p; a.errflag = h->d_flags;
-        a.nmax_word = h->fw + 1;           // (annp_fe_desc_sh raises it itself; the pair-loop descriptor kernel does not)
-        const bool desc_sh = !h->fe_desc_pairs && !h->fe_dense;
-        if ((rc = launch_fe_desc(h, a, inum, cap_list, max_numneigh, s))) return rc;
-        if (!desc_sh) hipLaunchKernelGGL(annp_max_int, dim3(annp_max_int_blocks(inum)), dim3(256), 0, s, h->ncount.p, inum, h->fw + 1);
-        HIP_TRY(h, hipGetLastError());
-        if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev[1], s)); HIP_TRY(h, hipEventRecord(h->ev[2], s)); }
-        // pass 2: network, ADP sums, energy, forces
-        AnnaArgs q{};
-        q.inum = inum; q.ilist = d_ilist; q.x = d_x; q.numneigh = d_numneigh; q.first = d_first; q.neigh = d_neigh;
-        q.n_cap = 64 * ANNA_NR; q.rc = h->cut; q.G = h->G.p; q.net = h->d_net;
-        q.net_doubles = h->net_doubles; q.net_in_lds = h->net_doubles <= ANNA_NET_LDS_MAX;
-        q.nl = h->nl; q.nin = h->nsf_dev; q.nnod = h->nnod; q.nout = h->nout;
-        for (int l = 0; l < h->nl; l++) q.actp |= (unsigned)(h->flagact[l] & 15) << (4 * l);
-        for (int k = 0; k < 17; k++) q.gp[k] = h->gp[k];
-        q.e_base = h->e_base;
-        q.f = d_f; q.eatom = d_eatom; q.eng = d_eng; q.virial = vtab; q.vatom = d_vatom; q.errflag = h->d_flags;
-        const size_t lds2 = anna_lds_per_wave(q.n_cap) * ANNP_WAVES_PER_BLOCK + anna_lds_net(h->net_doubles);
-        if (h->pre_force_wait) { HIP_TRY(h, hipStreamWaitEvent(s, h->pre_force_wait, 0)); h->pre_force_wait = nullptr; }
-        if (d_virial || d_vatom) hipLaunchKernelGGL((annp_anna_adp<true>), dim3(anna_blocks(inum)), dim3(256), lds2, s, q);
-        else hipLaunchKernelGGL((annp_anna_adp<false>), dim3(anna_blocks(inum)), dim3(256), lds2, s, q);
-        HIP_TRY(h, hipGetLastError());
-        // more in-range neighbours than a wave holds (128): the error word stays set on the device until the host
-        // has seen it, so it is reported by the next call or annp_hip_sync however many evaluations are enqueued
-        h->cap_last = q.n_cap;
-    } else {
-        NiArgs a{};
-        a.inum = inum; a.ilist = d_ilist; a.x = d_x; a.numneigh = d_numneigh; a.first = d_first; a.neigh = d_neigh;
-        a.npsf = h->npsf; a.ntsf = h->ntsf; a.sym = h->d_sym; a.isym = h->d_isym; a.compat = h->ni_compat;
-        a.type = types; a.active = h->active;
-        a.rc_rad = h->sym_rad[2]; a.rc_ang = h->sym_ang[3];
-        a.por_rad = ANNP_MY_PI / a.rc_rad; a.por_ang = ANNP_MY_PI / a.rc_ang;
-        a.rc2a = (a.rc_ang / ANNP_CFLENGTH) * (a.rc_ang / ANNP_CFLENGTH) * (1.0 + 1e-12);
-        for (int k = 0; k < 4; k++) { a.lam[k] = h->ni_lam[k]; a.eta[k] = h->ni_eta[k]; }
-        a.rad_em = h->ni_rad_em;
-        a.G = h->G.p; a.coef = h->coef.p; a.f = d_f; a.virial = vtab; a.vatom = d_vatom; a.ncount = h->ncount.p; a.errflag = h->d_flags;
-        if (a.npsf > NI_MAXP || a.ntsf > NI_MAXT)
-            return fail(h, ANNP_HIP_ESHAPE, "Behler kernels support npsf<=%d ntsf<=%d", NI_MAXP, NI_MAXT);
-        const int cap_max = ni_max_cap(true, h->nsf);
-        int cap_force;
-        // room for the pair lists the descriptor pass hands to the force pass: n_cap (n_cap - 1) / 2 entries of 2 bytes per
-        // atom (190 at capacity 20).  Not for very long records (the force pass then finds its pairs itself).
-        auto pair_room = [&](NiArgs &q) -> int {
-            q.pairs = nullptr; q.npair = nullptr; q.pstride = 0;
-            const long long ps = round_up(q.n_cap * (q.n_cap - 1) / 2, 8);
-            if (h->ni_no_pairs || ps > 2048 || (long long)inum * ps * 2 > (3ll << 30)) return 0;
-            int r;
-            if ((r = ensure(h, h->ni_pairs, (size_t)inum * ps)) || (r = ensure(h, h->ni_npair, (size_t)inum))) return r;
-            q.pairs = h->ni_pairs.p; q.npair = h->ni_npair.p; q.pstride = (int)ps;
-            return 0;
-        };
-        // Records: n_cap per atom from the previous evaluation's maximum.  A group of four atoms that has more is queued by the
-        // descriptor pass and taken, pass by pass, by a second small launch whose records hold a whole list row (cap_big), so
-        // the evaluation is complete whatever the configuration did since the capacity was learned.  An error remains only
-        // for more in-range neighbours than the largest records LDS can hold, or a list row longer than the caller said.
-        a.n_cap = std::min(h->ni_cap, cap_max);
-        if ((rc = ensure(h, h->ni_nbr, (size_t)inum * a.n_cap)) || (rc = pair_room(a))) return rc;
-        a.nbr = h->ni_nbr.p; a.nbr_stride = a.n_cap;
-        const int cap_big = std::min(cap_max, std::max(a.n_cap, round_up(std::max(max_numneigh, 8), 8)));
-        const bool fixup = cap_big > a.n_cap && !h->ni_no_fixup;
-        const int ngroups = (inum + NI_GA - 1) / NI_GA;
-        a.ovf_count = h->fw + 2; a.ovf_list = nullptr; a.ovf_cap = 0; a.fix = 0; a.skip_above = a.n_cap;
-        if (fixup) {
-            if ((rc = ensure(h, h->ovf, (size_t)ngroups)) || (rc = ensure(h, h->ni_fix_nbr, (size_t)ngroups * NI_GA * cap_big))) return rc;
-            a.ovf_list = h->ovf.p; a.ovf_cap = ngroups;
-        }
-        NiArgs b = a;           // the fix-up launches
-        b.fix = 1; b.n_cap = cap_big; b.nbr = h->ni_fix_nbr.p; b.nbr_stride = cap_big; b.pairs = nullptr; b.pstride = 0;
-        ni_launch_desc(a, h->ni_shape, s);
-        HIP_TRY(h, hipGetLastError());
-        if (fixup) { ni_launch_desc_fix(b, h->ni_shape, s); HIP_TRY(h, hipGetLastError()); }
-        hipLaunchKernelGGL(annp_max_int, dim3(annp_max_int_blocks(inum)), dim3(256), 0, s, h->ncount.p, inum, h->fw + 1);
-        HIP_TRY(h, hipGetLastError());
-        cap_force = a.n_cap;
-        if (!h->ni_primed) {    // first evaluation on the handle (or the one after an error): look at the counts once
-            if (int rc2 = copy_flags(h, s)) return rc2;
-            HIP_TRY(h, hipStreamSynchronize(s));
-            if (h->h_flags[0] > 0) {
-                h->reset_err = true;
-                h->ni_cap = std::min(cap_max, round_up(h->h_flags[0] + 2, 8));
-                return fail(h, ANNP_HIP_ENEIGHCAP, "%d neighbours inside the descriptor cutoff exceed the kernel capacity %d (list rows: %d)",
-                            h->h_flags[0], cap_big, max_numneigh);
-            }
-            h->ni_cap = ni_next_cap(h->h_flags[1]);
-            h->ni_primed = true;
-            cap_force = std::max(8, std::min(a.n_cap, round_up(h->h_flags[1], 2)));     // (fewer LDS bytes: more resident workgroups)
-        }
-        if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[1], s));
-        m.act_plain = 1; m.energy_raw = 1;
-        if ((rc = run_mlp_elements(h, m, s))) return rc;
-        if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[2], s));
-        a.n_cap = cap_force;
-        h->cap_last = cap_force;
-        if (h->pre_force_wait) { HIP_TRY(h, hipStreamWaitEvent(s, h->pre_force_wait, 0)); h->pre_force_wait = nullptr; }
-        ni_launch_force(a, h->ni_shape, d_virial != nullptr || d_vatom != nullptr, s);
-        HIP_TRY(h, hipGetLastError());
-        if (fixup) { ni_launch_force_fix(b, h->ni_shape, d_virial != nullptr || d_vatom != nullptr, s); HIP_TRY(h, hipGetLastError()); }
-    }
-    if (virial_caller) {
+    bool ran_sh = false;
+    if (h->descriptor == ANNP_HIP_DESC_CHEBYSHEV) rc = evaluate_chebyshev(h, e, m, ran_sh);
+    else if (h->descriptor == ANNP_HIP_DESC_ANNA_ADP) rc = evaluate_anna_adp(h, e);
+    else rc = evaluate_behler(h, e, m);
+    if (rc) return rc;
+
+    double *vtab = e.vtab;
+    if (fdotr) {
         vtab = h->d_vslots;
         HIP_TRY(h, hipMemsetAsync(vtab, 0, sizeof(double) * 8 * ANNP_VSLOTS, s));
-        hipLaunchKernelGGL(annp_fdotr_add, dim3(std::max(1, std::min(ANNP_VSLOTS, (nall + 255) / 256))), dim3(256), 0, s, nall, d_x, h->fscratch.p, f_caller, vtab);
+        hipLaunchKernelGGL(annp_fdotr_add, dim3(std::max(1, std::min(ANNP_VSLOTS, (nall + 255) / 256))), dim3(256), 0, s, nall, d_x, h->fscratch.p, d_f, vtab);
         HIP_TRY(h, hipGetLastError());
-        d_virial = virial_caller;
     }
     if (vtab) {
         hipLaunchKernelGGL(annp_virial_fold, dim3(1), dim3(1024), 0, s, vtab, d_virial);
         HIP_TRY(h, hipGetLastError());
     }
-    // flag words of this evaluation, for whoever looks next (poll_flags)
-    HIP_TRY(h, hipEventRecord(h->ev_tail, s));
-    HIP_TRY(h, hipStreamWaitEvent(h->stream_flags, h->ev_tail, 0));
-    if (int rc2 = copy_flags(h, h->stream_flags)) return rc2;
-    HIP_TRY(h, hipEventRecord(h->ev_flags, h->stream_flags));
-    HIP_TRY(h, hipMemsetAsync(h->fw + 1, 0, (ANNP_NFLAGS - 1) * sizeof(int), h->stream_flags));
-    HIP_TRY(h, hipEventRecord(h->ev_set[h->flags_par], h->stream_flags));
-    h->set_used[h->flags_par] = true;
-    h->flags_pending = true; h->flags_dirty = false;
-    h->flags_sh = h->fe_last_sh; h->flags_inum = h->fe_last_inum;      // (what digest_flags judges the queue length by)
-
-    if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev[3], s)); h->ev_count++; }
-    (void)nall; (void)d_type;
-    return 0;
+    if ((rc = h->flags.hand_over(h, s, ran_sh, inum))) return rc;
+    return record_timing(h, 3, s);
 }
 
 // ---- the halo wire: RCCL point-to-point, called from here --------------------------------------------------------------
@@ -962,6 +1097,25 @@ int ensure_pool(annp_hip_handle *h)
     return 0;
 }
 
+// The switches a handle takes from the environment, once, at init (INTEGRATION.md has the table; ANNP_HIP_COPY_THREADS is read where the
+// copy threads are started, ensure_pool)
+void read_switches(annp_hip_handle *h)
+{
+    if (const char *e = std::getenv("ANNP_HIP_REGISTER")) h->use_register = std::atoi(e) != 0;
+    if (const char *e = std::getenv("ANNP_HIP_FULL_LIST")) h->full_list = std::atoi(e) != 0;
+    if (const char *e = std::getenv("ANNP_HIP_NEIGH_SYNC")) h->nb.lazy = std::atoi(e) == 0;
+    if (const char *e = std::getenv("ANNP_HIP_NI_PAIRS")) h->ni_no_pairs = std::atoi(e) == 0;
+    if (const char *e = std::getenv("ANNP_HIP_NI_FIXUP")) h->ni_no_fixup = std::atoi(e) == 0;
+    if (const char *e = std::getenv("ANNP_HIP_FE_DESC")) h->fe_desc_pairs = std::strcmp(e, "pairs") == 0;
+    if (const char *e = std::getenv("ANNP_HIP_FE_FORCE")) h->fe_force_pairs = std::strcmp(e, "pairs") == 0;
+    if (const char *e = std::getenv("ANNP_HIP_VIRIAL")) h->virial_tally = std::strcmp(e, "tally") == 0;
+    if (const char *e = std::getenv("ANNP_HIP_SHF_PLACES")) h->shf_places_by_number = std::strcmp(e, "number") == 0;
+    if (const char *e = std::getenv("ANNP_HIP_LIST_PARTS")) h->list_parts = std::max(1, std::min((int)annp_hip_handle::kListParts, std::atoi(e)));
+    if (const char *e = std::getenv("ANNP_HIP_LIST_PIPE_MIN")) h->list_pipe_min = std::max(1, std::atoi(e));
+    if (const char *e = std::getenv("ANNP_HIP_LIST_CHUNK")) h->list_chunk = std::max<size_t>(1024, std::min<size_t>(annp_hip_handle::kListChunk, (size_t)std::atoll(e)));
+    if (const char *e = std::getenv("ANNP_HIP_SH_CAP")) h->sh_cap = std::min((int)SH_CAP_MAX, std::max((int)SH_CAP_MIN, round_up(std::atoi(e), 16)));
+}
+
 // pinned staging buffers (32 MB each) + their events, shared by the host-list upload and the list hand-back
 int ensure_list_staging(annp_hip_handle *h)
 {
@@ -1014,12 +1168,7 @@ void annp_hip_clear(annp_hip_handle *h)
     neigh_release(h->nb);
     if (h->d_scalars) (void)hipFree(h->d_scalars);
     if (h->d_vslots) (void)hipFree(h->d_vslots);
-    if (h->d_flags) (void)hipFree(h->d_flags);
-    if (h->h_flags) (void)hipHostFree(h->h_flags);
-    if (h->ev_flags) (void)hipEventDestroy(h->ev_flags);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    for (int k = 0; k < 2; k++) if (h->ev_set[k]) (void)hipEventDestroy(h->ev_set[k]);
-    if (h->stream_flags) (void)hipStreamDestroy(h->stream_flags);
+    h->flags.release();
     if (h->reg_x.ok && hipHostUnregister(const_cast<void *>(h->reg_x.ptr)) != hipSuccess) (void)hipGetLastError();
     if (h->reg_f.ok && hipHostUnregister(const_cast<void *>(h->reg_f.ptr)) != hipSuccess) (void)hipGetLastError();
     if (h->pin_x) (void)hipHostFree(h->pin_x);
@@ -1126,30 +1275,15 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
     DeviceGuard guard_(device);
     INIT_TRY(guard_.err);
     INIT_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    INIT_TRY(hipEventCreateWithFlags(&h->ev_flags, hipEventDisableTiming));
-    INIT_TRY(hipStreamCreateWithFlags(&h->stream_flags, hipStreamNonBlocking));
-    INIT_TRY(hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));
+    INIT_TRY(hipEventCreateWithFlags(&h->flags.ev_landed, hipEventDisableTiming));
+    INIT_TRY(hipStreamCreateWithFlags(&h->flags.side, hipStreamNonBlocking));
+    INIT_TRY(hipEventCreateWithFlags(&h->flags.ev_tail, hipEventDisableTiming));
     INIT_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     INIT_TRY(hipEventCreateWithFlags(&h->ev_f_up, hipEventDisableTiming));
-    if (const char *e = std::getenv("ANNP_HIP_REGISTER")) h->use_register = std::atoi(e) != 0;
+    read_switches(h);
     h->descriptor = p->descriptor; h->ntypes = p->ntypes; h->ntl = p->ntl; h->nhl = p->nhl; h->nnod = p->nnod;
     h->nsf = p->nsf; h->npsf = p->npsf; h->ntsf = p->ntsf; h->nl = nl; h->ni_compat = p->ni_compat;
     h->e_scale = p->e_scale; h->e_shift = p->e_shift; h->e_atom = p->e_atom; h->cut = p->cut;
-    if (const char *e = std::getenv("ANNP_HIP_FULL_LIST")) h->full_list = std::atoi(e) != 0;
-    if (const char *e = std::getenv("ANNP_HIP_NEIGH_SYNC")) h->nb.lazy = std::atoi(e) == 0;
-    if (const char *e = std::getenv("ANNP_HIP_NI_PAIRS")) h->ni_no_pairs = std::atoi(e) == 0;
-    if (const char *e = std::getenv("ANNP_HIP_NI_FIXUP")) h->ni_no_fixup = std::atoi(e) == 0;
-    if (const char *e = std::getenv("ANNP_HIP_FE_DESC")) h->fe_desc_pairs = std::strcmp(e, "pairs") == 0;
-    if (const char *e = std::getenv("ANNP_HIP_FE_FORCE")) h->fe_force_pairs = std::strcmp(e, "pairs") == 0;
-    if (const char *e = std::getenv("ANNP_HIP_VIRIAL")) h->virial_tally = std::strcmp(e, "tally") == 0;
-    if (const char *e = std::getenv("ANNP_HIP_SHF_PLACES")) h->shf_places_by_number = std::strcmp(e, "number") == 0;
-    if (const char *e = std::getenv("ANNP_HIP_SH_WPB")) h->sh_wpb = std::min(4, std::max(0, std::atoi(e)));
-    if (const char *e = std::getenv("ANNP_HIP_REPLAN_IMAGES")) h->rp_images_by_dimension = std::strcmp(e, "dims") == 0;
-    if (const char *e = std::getenv("ANNP_HIP_LIST_PARTS")) h->list_parts = std::max(1, std::min((int)annp_hip_handle::kListParts, std::atoi(e)));
-    if (const char *e = std::getenv("ANNP_HIP_LIST_PIPE_MIN")) h->list_pipe_min = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("ANNP_HIP_LIST_CHUNK")) h->list_chunk = std::max<size_t>(1024, std::min<size_t>(annp_hip_handle::kListChunk, (size_t)std::atoll(e)));
-    if (const char *e = std::getenv("ANNP_HIP_SH_TAIL")) h->sh_group = std::strcmp(e, "group") == 0;
-    if (const char *e = std::getenv("ANNP_HIP_SH_CAP")) h->sh_cap = std::min((int)SH_CAP_MAX, std::max((int)SH_CAP_MIN, round_up(std::atoi(e), 16)));
     h->cutsq = cutsq_all;
     h->nelem = ne; h->multi = multi; h->active = active;
     if (multi) {
@@ -1351,20 +1485,14 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
     }
     INIT_TRY(hipMalloc((void **)&h->d_scalars, 8 * sizeof(double)));
     INIT_TRY(hipMalloc((void **)&h->d_vslots, sizeof(double) * 8 * ANNP_VSLOTS));
-    INIT_TRY(hipMalloc((void **)&h->d_flags, 3 * ANNP_NFLAGS * sizeof(int)));       // the sticky word's row and two sets of per-evaluation words
-    INIT_TRY(hipMemset(h->d_flags, 0, 3 * ANNP_NFLAGS * sizeof(int)));
-    h->fw = h->d_flags + ANNP_NFLAGS;
-    INIT_TRY(hipEventCreateWithFlags(&h->ev_set[0], hipEventDisableTiming));
-    INIT_TRY(hipEventCreateWithFlags(&h->ev_set[1], hipEventDisableTiming));
-    INIT_TRY(hipHostMalloc((void **)&h->h_flags, ANNP_NFLAGS * sizeof(int)));
+    INIT_TRY(h->flags.allocate());
     INIT_TRY(hipHostMalloc((void **)&h->h_scalars, 8 * sizeof(double)));
     h->bytes += 8 * sizeof(double) + ANNP_NFLAGS * sizeof(int) + sizeof(double) * 8 * ANNP_VSLOTS;
     // kernels may ask for the whole LDS
     {
         const int full = 160 * 1024;
         INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_desc<FE_NP, FE_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
-        INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_desc_sh<FE_NP, FE_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
-        INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_desc_sh<FE_NP, FE_NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
+        INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_desc_sh<FE_NP, FE_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
         INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_desc_fixup<FE_NP, FE_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
         INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_force_sh<FE_NP, FE_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
         INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_force_sh<FE_NP, FE_NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
@@ -1495,18 +1623,14 @@ int annp_hip_sync(annp_hip_handle *h)
         std::string msg;
         if (int rc = neigh_settle(h->nb, msg)) return fail(h, rc, "%s", msg.c_str());
     }
-    return poll_flags(h, true);
+    return h->flags.poll(h, true);
 }
 
 int annp_hip_eval_path(annp_hip_handle *h)
 {
     if (!h) return ANNP_HIP_EARG;
     DEVICE_GUARD(h);
-    if (h->flags_pending) {
-        HIP_TRY(h, hipEventSynchronize(h->ev_flags));
-        h->flags_pending = false;
-        digest_flags(h);
-    }
+    if (int rc = h->flags.settle(h, true)) return rc;
     if (h->descriptor == ANNP_HIP_DESC_BEHLER) return 3;
     if (h->descriptor == ANNP_HIP_DESC_ANNA_ADP) return 4;
     if (h->fe_desc_pairs || h->fe_force_pairs) return 2;
@@ -1528,11 +1652,7 @@ int annp_hip_eval_info(annp_hip_handle *h, int *info4)
 {
     if (!h || !info4) return ANNP_HIP_EARG;
     DEVICE_GUARD(h);
-    if (h->flags_pending) {     // the error, if any, stays for the next call or annp_hip_sync to report
-        HIP_TRY(h, hipEventSynchronize(h->ev_flags));
-        h->flags_pending = false;
-        digest_flags(h);
-    }
+    if (int rc = h->flags.settle(h, true)) return rc;     // the error, if any, stays for the next call or annp_hip_sync to report
     for (int k = 0; k < 4; k++) info4[k] = h->info[k];
     return 0;
 }
@@ -1866,7 +1986,7 @@ int annp_hip_replan_images(annp_hip_handle *h, int np0, double *d_x, long long c
     // With buffers to fill (the usual call) the dimensions follow one another without the host looking at their counts in between
     // (round 6: one wait per call instead of one per dimension): the kernels take the number of rows held so far from device memory
     // and cover the buffer's capacity; a dimension that does not fit writes nothing and the caller is told how many rows were wanted.
-    if (d_root && d_shift && capacity_rows <= 0x7fffffffll / 3 && !h->rp_images_by_dimension) {
+    if (d_root && d_shift && capacity_rows <= 0x7fffffffll / 3) {
         int rc;
         const int cap = (int)capacity_rows;
         if ((rc = rp_scratch(h, 2 * (size_t)cap + 8, 2 * (size_t)cap + 8))) return rc;
@@ -1938,7 +2058,7 @@ int annp_hip_replan_fold_plan(annp_hip_handle *h, int m, const int *d_targets, i
     if ((rc = ensure(h, h->rp_cnt, 2 * (size_t)nkeys + 8)) || (rc = rp_scratch(h, 8, (size_t)nkeys + 8))) return rc;
     int *cnt = h->rp_cnt.p, *cursor = cnt + nkeys + 4;
     HIP_TRY(h, hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)nkeys, s));
-    if (m > 0) hipLaunchKernelGGL(annp_replan_count, dim3((m + 255) / 256), dim3(256), 0, s, m, d_targets, nkeys, cnt, h->d_flags);
+    if (m > 0) hipLaunchKernelGGL(annp_replan_count, dim3((m + 255) / 256), dim3(256), 0, s, m, d_targets, nkeys, cnt, h->flags.word(FLAG_OVER));
     rp_scan(h, cnt, nkeys, h->rp_pos.p, h->rp_bs.p, 0, s);
     HIP_TRY(h, hipMemcpyAsync(h->rp_pos.p + nkeys, h->rp_tot, sizeof(long long), hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(annp_replan_start32, dim3((nkeys + 256) / 256), dim3(256), 0, s, nkeys, h->rp_pos.p, d_start, cursor);
@@ -2029,7 +2149,7 @@ static int host_finish(annp_hip_handle *h, int inum, int nall, int eflag, int vf
     int rc;
     HIP_TRY(h, hipMemcpyAsync(h->h_scalars, h->d_scalars, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
-    if (int rcf = poll_flags(h, true)) return rcf;
+    if (int rcf = h->flags.poll(h, true)) return rcf;
     const size_t nf = (size_t)nall * 3;
     if (f_on_device) {          // h->f started from the caller's f: the sum comes back into place
         HIP_TRY(h, hipMemcpyAsync(f, h->f.p, sizeof(double) * nf, hipMemcpyDeviceToHost, s));
@@ -2056,7 +2176,75 @@ static int host_finish(annp_hip_handle *h, int inum, int nall, int eflag, int vf
     return 0;
 }
 
-// Positions are on the device (h->x); run one evaluation on the handle's stream and bring the results back.
+// ---- one evaluation for the host-pointer entry points: positions are on the device (h->x), results go back through host_finish
+struct HostEval {
+    const int *d_type = nullptr;        // h->type when the potential distinguishes atom types
+    bool f_on_device = false;           // the caller's f is page-locked: the device accumulates on top of it and the sum is copied back into place
+    bool want_eatom = false;
+};
+
+// What an evaluation accumulates into, as it must be when its first kernel runs: f uploaded on the second stream while the descriptor
+// and network passes run (the force pass waits for it: pre_force_wait) or zeroed, scalars and per-atom arrays zeroed.  Once per attempt.
+static int host_start_outputs(annp_hip_handle *h, int nall, const double *f, bool vatom, const HostEval &he)
+{
+    hipStream_t s = h->stream;
+    const size_t nf = (size_t)nall * 3;
+    if (he.f_on_device) {
+        HIP_TRY(h, hipMemcpyAsync(h->f.p, f, nf * sizeof(double), hipMemcpyHostToDevice, h->stream2));
+        HIP_TRY(h, hipEventRecord(h->ev_f_up, h->stream2));
+        h->pre_force_wait = h->ev_f_up;
+    } else {
+        HIP_TRY(h, hipMemsetAsync(h->f.p, 0, sizeof(double) * nf, s));
+    }
+    HIP_TRY(h, hipMemsetAsync(h->d_scalars, 0, 8 * sizeof(double), s));
+    if (he.want_eatom) HIP_TRY(h, hipMemsetAsync(h->eatom.p, 0, sizeof(double) * (size_t)nall, s));
+    if (vatom) HIP_TRY(h, hipMemsetAsync(h->vatom.p, 0, sizeof(double) * (size_t)nall * 6, s));
+    return 0;
+}
+
+// Once per call: the copy threads, room for the results, the atom types checked and uploaded, the caller's f page-locked where it
+// lies (no host loop over f), and the outputs of the first attempt started
+static int host_begin(annp_hip_handle *h, int nall, const int *host_type, int eflag, int eatom_flag,
+                      const double *f, const double *eatom, bool vatom, HostEval &he)
+{
+    int rc;
+    if ((rc = ensure_pool(h))) return rc;
+    if ((rc = ensure(h, h->f, (size_t)nall * 3)) || (rc = ensure(h, h->eatom, (size_t)nall))) return rc;
+    if (vatom && (rc = ensure(h, h->vatom, (size_t)nall * 6))) return rc;
+    if (h->multi) {             // atom types select the element's network (and drop atoms of unmapped types)
+        if (!host_type) return fail(h, ANNP_HIP_EARG, "this potential distinguishes atom types: host_type is required");
+        for (int k = 0; k < nall; k++)          // map[type] and the type's bit of `active` are indexed with it on the device
+            if (host_type[k] < 1 || host_type[k] > h->ntypes)
+                return fail(h, ANNP_HIP_EARG, "type[%d] = %d is outside 1..%d", k, host_type[k], h->ntypes);
+        if ((rc = ensure(h, h->type, (size_t)nall))) return rc;
+        HIP_TRY(h, hipMemcpyAsync(h->type.p, host_type, sizeof(int) * (size_t)nall, hipMemcpyHostToDevice, h->stream));
+        he.d_type = h->type.p;
+    }
+    he.want_eatom = eflag && eatom_flag && eatom;
+    he.f_on_device = nall > 0 && host_register(h, h->reg_f, f, (size_t)nall * 3 * sizeof(double));
+    return host_start_outputs(h, nall, f, vatom, he);
+}
+
+// an evaluation that returned before its force pass (error, inum == 0, no run of a list got that far): the upload of f still has to
+// land before anything else happens to it
+static void drain_pre_force_wait(annp_hip_handle *h)
+{
+    if (h->pre_force_wait) {
+        (void)hipStreamWaitEvent(h->stream, h->pre_force_wait, 0);
+        h->pre_force_wait = nullptr;
+    }
+}
+
+// the evaluation of list slots [ii0, ii0 + n) of a list on the device, into the handle's copies of the caller's arrays
+static int host_compute(annp_hip_handle *h, int n, int nall, const HostEval &he, const int *d_ilist, const int *d_numneigh, const long long *d_first,
+                        const int *d_neigh, int max_numneigh, bool want_virial, bool vatom)
+{
+    return compute_device_impl(h, n, nall, h->x.p, he.d_type, d_ilist, d_numneigh, d_first, d_neigh, max_numneigh,
+                               h->f.p, he.want_eatom ? h->eatom.p : nullptr, h->d_scalars, want_virial ? h->d_scalars + 1 : nullptr,
+                               vatom ? h->vatom.p : nullptr, h->stream);
+}
+
+// Run one evaluation on the handle's stream and bring the results back.
 // A Behler capacity overflow is not an error here: the call is synchronous anyway, so it runs the evaluation
 // again with the raised capacity.
 static int host_evaluate(annp_hip_handle *h, int inum, int nall, const int *host_type, const int *d_ilist,
@@ -2064,46 +2252,15 @@ static int host_evaluate(annp_hip_handle *h, int inum, int nall, const int *host
                          int eflag, int vflag, int eatom_flag,
                          double *f, double *eng_vdwl, double *eatom, double *virial, double *vatom)
 {
-    hipStream_t s = h->stream;
     int rc;
-    if ((rc = ensure_pool(h))) return rc;
-    if ((rc = ensure(h, h->f, (size_t)nall * 3)) || (rc = ensure(h, h->eatom, (size_t)nall))) return rc;
-    if (vatom && (rc = ensure(h, h->vatom, (size_t)nall * 6))) return rc;
-    const int *d_type = nullptr;
-    if (h->multi) {             // atom types select the element's network (and drop atoms of unmapped types)
-        if (!host_type) return fail(h, ANNP_HIP_EARG, "this potential distinguishes atom types: host_type is required");
-        for (int k = 0; k < nall; k++)          // map[type] and the type's bit of `active` are indexed with it on the device
-            if (host_type[k] < 1 || host_type[k] > h->ntypes)
-                return fail(h, ANNP_HIP_EARG, "type[%d] = %d is outside 1..%d", k, host_type[k], h->ntypes);
-        if ((rc = ensure(h, h->type, (size_t)nall))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->type.p, host_type, sizeof(int) * (size_t)nall, hipMemcpyHostToDevice, s));
-        d_type = h->type.p;
-    }
-    const bool want_eatom = eflag && eatom_flag && eatom;
-    const size_t nf = (size_t)nall * 3;
-    // f: the device accumulates on top of the caller's values, uploaded on a second stream while the descriptor and
-    // network passes run (the force pass waits for it), and the sum is copied back into place -- no host loop over f
-    const bool f_on_device = nall > 0 && host_register(h, h->reg_f, f, nf * sizeof(double));
+    HostEval he;
+    if ((rc = host_begin(h, nall, host_type, eflag, eatom_flag, f, eatom, vatom != nullptr, he))) return rc;
     for (int attempt = 0;; attempt++) {
-        if (f_on_device) {
-            HIP_TRY(h, hipMemcpyAsync(h->f.p, f, nf * sizeof(double), hipMemcpyHostToDevice, h->stream2));
-            HIP_TRY(h, hipEventRecord(h->ev_f_up, h->stream2));
-            h->pre_force_wait = h->ev_f_up;
-        } else {
-            HIP_TRY(h, hipMemsetAsync(h->f.p, 0, sizeof(double) * nf, s));
-        }
-        HIP_TRY(h, hipMemsetAsync(h->d_scalars, 0, 8 * sizeof(double), s));
-        if (want_eatom) HIP_TRY(h, hipMemsetAsync(h->eatom.p, 0, sizeof(double) * (size_t)nall, s));
-        if (vatom) HIP_TRY(h, hipMemsetAsync(h->vatom.p, 0, sizeof(double) * (size_t)nall * 6, s));
-        rc = compute_device_impl(h, inum, nall, h->x.p, d_type, d_ilist, d_numneigh, d_first, d_neigh, max_numneigh,
-                                 h->f.p, want_eatom ? h->eatom.p : nullptr, h->d_scalars, (vflag && virial) ? h->d_scalars + 1 : nullptr,
-                                 vatom ? h->vatom.p : nullptr, s);
-        if (h->pre_force_wait) {        // the evaluation returned before its force pass (error, inum == 0): the upload still has to land
-            (void)hipStreamWaitEvent(s, h->pre_force_wait, 0);
-            h->pre_force_wait = nullptr;
-        }
-        if (!rc) rc = host_finish(h, inum, nall, eflag, vflag, eatom_flag, f_on_device, f, eng_vdwl, eatom, virial, vatom);
-        else (void)hipStreamSynchronize(s);
+        if (attempt > 0 && (rc = host_start_outputs(h, nall, f, vatom != nullptr, he))) return rc;
+        rc = host_compute(h, inum, nall, he, d_ilist, d_numneigh, d_first, d_neigh, max_numneigh, vflag && virial, vatom != nullptr);
+        drain_pre_force_wait(h);
+        if (!rc) rc = host_finish(h, inum, nall, eflag, vflag, eatom_flag, he.f_on_device, f, eng_vdwl, eatom, virial, vatom);
+        else (void)hipStreamSynchronize(h->stream);
         if (rc == ANNP_HIP_ENEIGHCAP && attempt == 0 && h->descriptor == ANNP_HIP_DESC_BEHLER && !h->ni_primed) continue;
         return rc;
     }
@@ -2200,47 +2357,18 @@ static int host_evaluate_uploading(annp_hip_handle *h, int inum, int nall, const
                                    const int *const *firstneigh, int eflag, int vflag, int eatom_flag,
                                    double *f, double *eng_vdwl, double *eatom, double *virial, double *vatom)
 {
-    hipStream_t s = h->stream;
     int rc;
-    if ((rc = ensure_pool(h))) return rc;
-    if ((rc = ensure(h, h->f, (size_t)nall * 3)) || (rc = ensure(h, h->eatom, (size_t)nall))) return rc;
-    if (vatom && (rc = ensure(h, h->vatom, (size_t)nall * 6))) return rc;
-    const int *d_type = nullptr;
-    if (h->multi) {
-        if (!host_type) return fail(h, ANNP_HIP_EARG, "this potential distinguishes atom types: host_type is required");
-        for (int k = 0; k < nall; k++)
-            if (host_type[k] < 1 || host_type[k] > h->ntypes)
-                return fail(h, ANNP_HIP_EARG, "type[%d] = %d is outside 1..%d", k, host_type[k], h->ntypes);
-        if ((rc = ensure(h, h->type, (size_t)nall))) return rc;
-        HIP_TRY(h, hipMemcpyAsync(h->type.p, host_type, sizeof(int) * (size_t)nall, hipMemcpyHostToDevice, s));
-        d_type = h->type.p;
-    }
-    const bool want_eatom = eflag && eatom_flag && eatom;
-    const size_t nf = (size_t)nall * 3;
-    const bool f_on_device = nall > 0 && host_register(h, h->reg_f, f, nf * sizeof(double));
-    if (f_on_device) {          // (ahead of the list on the second stream: the first run's force pass waits for it)
-        HIP_TRY(h, hipMemcpyAsync(h->f.p, f, nf * sizeof(double), hipMemcpyHostToDevice, h->stream2));
-        HIP_TRY(h, hipEventRecord(h->ev_f_up, h->stream2));
-        h->pre_force_wait = h->ev_f_up;
-    } else {
-        HIP_TRY(h, hipMemsetAsync(h->f.p, 0, sizeof(double) * nf, s));
-    }
-    HIP_TRY(h, hipMemsetAsync(h->d_scalars, 0, 8 * sizeof(double), s));
-    if (want_eatom) HIP_TRY(h, hipMemsetAsync(h->eatom.p, 0, sizeof(double) * (size_t)nall, s));
-    if (vatom) HIP_TRY(h, hipMemsetAsync(h->vatom.p, 0, sizeof(double) * (size_t)nall * 6, s));
+    HostEval he;
+    // (f goes ahead of the list on the second stream: the first run's force pass waits for it)
+    if ((rc = host_begin(h, nall, host_type, eflag, eatom_flag, f, eatom, vatom != nullptr, he))) return rc;
     h->list_valid = false;
     rc = upload_host_list(h, inum, nall, ilist, numj, firstneigh, h->stream2, h->list_parts, [&](int a, int b, hipEvent_t ev) -> int {
-        HIP_TRY(h, hipStreamWaitEvent(s, ev, 0));
-        return compute_device_impl(h, b - a, nall, h->x.p, d_type, h->ilist.p + a, h->numneigh.p, h->first.p, h->neigh.p, h->list_max,
-                                   h->f.p, want_eatom ? h->eatom.p : nullptr, h->d_scalars, (vflag && virial) ? h->d_scalars + 1 : nullptr,
-                                   vatom ? h->vatom.p : nullptr, s);
+        HIP_TRY(h, hipStreamWaitEvent(h->stream, ev, 0));
+        return host_compute(h, b - a, nall, he, h->ilist.p + a, h->numneigh.p, h->first.p, h->neigh.p, h->list_max, vflag && virial, vatom != nullptr);
     });
-    if (h->pre_force_wait) {        // no run got as far as its force pass: the upload of f still has to land before anything else happens to it
-        (void)hipStreamWaitEvent(s, h->pre_force_wait, 0);
-        h->pre_force_wait = nullptr;
-    }
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    return host_finish(h, inum, nall, eflag, vflag, eatom_flag, f_on_device, f, eng_vdwl, eatom, virial, vatom);
+    drain_pre_force_wait(h);
+    if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+    return host_finish(h, inum, nall, eflag, vflag, eatom_flag, he.f_on_device, f, eng_vdwl, eatom, virial, vatom);
 }
 
 int annp_hip_compute(annp_hip_handle *h, int ago, int inum, int nall, int nghost,

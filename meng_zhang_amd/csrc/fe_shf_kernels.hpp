@@ -96,9 +96,6 @@ struct ShfTable {
 #endif
         const int b = j >> 3;
         unsigned h = ((unsigned)b * 0x9E3779B1u) >> (32 - SHF_BBITS);
-#ifdef ANNP_SHF_NOPROBE     // developer timing build (wrong forces): the bucket the hash names, whoever holds it -- what a probe costs
-        { double *a = acc + (h * SHF_BATOMS + (j & 7)) * 3; key[h] = b; atomicAdd(a, fx); atomicAdd(a + 1, fy); atomicAdd(a + 2, fz); return; }
-#endif
 #pragma unroll 1
         for (int probe = 0; probe < SHF_TPROBE; probe++) {
             // most contributions find their bucket taken by an earlier one: a plain read settles those, the compare-and-swap
@@ -367,9 +364,6 @@ struct ShfBuild {
     {
         if constexpr (M >= 0) {
             shf_convert_column<M>(tb, dump, conv, l);
-#ifdef SHP_FENCE_COLUMNS
-            asm volatile("" ::: "memory");
-#endif
             ShfBuild<WQ, IDX + 1>::convert(tb, dump, conv, l);
         }
     }
@@ -495,12 +489,7 @@ __device__ __forceinline__ void shf_turn(const FeArgs &p, const ShfAtom &at, con
         asm volatile("" : "+v"(z[u]), "+v"(wx[u]), "+v"(wy[u]), "+v"(al[u]), "+v"(be[u]), "+v"(g0[u]));
     }
     double U[CC], Ux[CC], Uy[CC], Uz[CC];
-#ifdef ANNP_SHF_SKIP_EVAL       // developer timing builds only: everything but the columns
-#pragma unroll
-    for (int u = 0; u < CC; u++) { U[u] = z[u]; Ux[u] = wx[u]; Uy[u] = wy[u]; Uz[u] = z[u] * wx[u]; }
-#else
     shf_evaluate<CC>(tb, z, wx, wy, U, Ux, Uy, Uz);
-#endif
     mid();
 #pragma unroll
     for (int u = 0; u < CC; u++) {
@@ -510,9 +499,7 @@ __device__ __forceinline__ void shf_turn(const FeArgs &p, const ShfAtom &at, con
             const double f0 = fma(t, wx[u], -al[u] * Ux[u]);
             const double f1 = fma(t, wy[u], -al[u] * Uy[u]);
             const double f2 = fma(t, z[u], -al[u] * Uz[u]);
-#ifndef ANNP_SHF_SKIP_ADD
             tab.add(jn[u], -f0, -f1, -f2);                    // F_a = -Fn_a to the neighbour, +Fn_a to the centre (fe:199-211)
-#endif
             fi[0] += f0; fi[1] += f1; fi[2] += f2;
             if (VIRIAL) {   // ev_tally_xyz(i,j,...,fx=-Fj, del = xi-xj = r e)   (fe:201-209)
                 const double d0 = rr[u] * wx[u], d1 = rr[u] * wy[u], d2 = rr[u] * z[u];
@@ -734,9 +721,7 @@ __global__ __launch_bounds__(64 * SHF_WAVES, ANNP_SHF_WPS) void annp_fe_force_sh
     SHF_STAMP(6);
     __syncthreads();
     SHF_STAMP(7);
-#ifndef ANNP_SHF_SKIP_FLUSH
     tab.flush(threadIdx.x, p.tab_spills);          // the workgroup's table, in memory order
-#endif
     if (VIRIAL && p.virial && threadIdx.x < 6) atomicAdd(&virial_row(p.virial)[threadIdx.x], tab.vacc()[threadIdx.x]);     // (annp_common.hpp: the global virial)
     SHF_STAMP(8);
 }
