@@ -287,6 +287,10 @@ int annp_hip_eval_info(annp_hip_handle *handle, int *info4);
  *      the maximum falls under 160 again)
  *   2  Chebyshev passes pair by pair because ANNP_HIP_FE_DESC / ANNP_HIP_FE_FORCE ask for it (developer A/B switches)
  *   3  Behler G2/G4 kernels      4  pair_style anna_adp kernels
+ *   5  Behler G2/G4, one kernel per evaluation (ANNP_HIP_NI_EVAL=fused when the handle was made): descriptor, network and force of an
+ *      atom group in one launch.  The first evaluation on a handle and the one after a capacity error run the passes (3), which size
+ *      the records; potentials with several networks and records too long for that kernel's LDS stay at 3.  Its timing events follow
+ *      the anna_adp convention: ms4[0] and [1] empty, [2] the kernel with its fix-up launch, [3] the whole evaluation.
  * The change 0 -> 1 is also announced once on the stream given to annp_hip_set_notice (annp_gpu_init passes LAMMPS' screen).
  * So is one more thing a caller would otherwise only see in its timings: atoms in no spatial order.  The force pass collects
  * forces in a table whose buckets hold eight atoms with consecutive indices; a caller that sorts its atoms in space (LAMMPS:

@@ -33,6 +33,7 @@
 #include "mlp_kernels.hpp"
 #include "neigh_kernels.hpp"
 #include "ni_kernels.hpp"
+#include "ni_fused_kernels.hpp"
 #include "anna_kernels.hpp"
 #include "step_kernels.hpp"
 #include "replan_kernels.hpp"
@@ -194,6 +195,8 @@ struct annp_hip_handle {
     int ni_compat = 0;
     bool ni_no_fixup = false;           // ANNP_HIP_NI_FIXUP=0: no queue behind the Behler records (overflow is an error again)
     bool ni_no_pairs = false;           // ANNP_HIP_NI_PAIRS=0: the Behler force pass finds its pairs itself (no lists through memory)
+    bool ni_fused = false;              // ANNP_HIP_NI_EVAL=fused: descriptor, network and force of a group in one kernel (ni_fused_kernels.hpp) once the capacity is known
+    double *d_ni_net = nullptr;         // ... its network image (ni_net_build); null: the potential is not covered (several networks), the passes run
     double *d_sym = nullptr;            // function tables (ni_kernels.hpp, "per-function tables")
     int *d_isym = nullptr;
     unsigned long long ni_rad_em = 0;   // NiArgs::rad_em
@@ -882,13 +885,11 @@ int evaluate_anna_adp(annp_hip_handle *h, const EvalArgs &e)
 }
 
 // pair_style annp, Behler descriptor: descriptor pass (+ fix-up) -> network pass -> force pass (+ fix-up)
-int evaluate_behler(annp_hip_handle *h, const EvalArgs &e, MlpArgs m)
+// what both Behler routes hand their kernels: the caller's arrays, the function tables, the work buffers every route writes
+NiArgs ni_args(annp_hip_handle *h, const EvalArgs &e)
 {
-    int rc;
-    const int inum = e.inum;
-    hipStream_t s = e.s;
     NiArgs a{};
-    a.inum = inum; a.ilist = e.ilist; a.x = e.x; a.numneigh = e.numneigh; a.first = e.first; a.neigh = e.neigh;
+    a.inum = e.inum; a.ilist = e.ilist; a.x = e.x; a.numneigh = e.numneigh; a.first = e.first; a.neigh = e.neigh;
     a.npsf = h->npsf; a.ntsf = h->ntsf; a.sym = h->d_sym; a.isym = h->d_isym; a.compat = h->ni_compat;
     a.type = e.types; a.active = h->active;
     a.rc_rad = h->sym_rad[2]; a.rc_ang = h->sym_ang[3];
@@ -896,7 +897,17 @@ int evaluate_behler(annp_hip_handle *h, const EvalArgs &e, MlpArgs m)
     a.rc2a = (a.rc_ang / ANNP_CFLENGTH) * (a.rc_ang / ANNP_CFLENGTH) * (1.0 + 1e-12);
     for (int k = 0; k < 4; k++) { a.lam[k] = h->ni_lam[k]; a.eta[k] = h->ni_eta[k]; }
     a.rad_em = h->ni_rad_em;
-    a.G = h->G.p; a.coef = h->coef.p; a.f = e.f; a.virial = e.vtab; a.vatom = e.vatom; a.ncount = h->ncount.p; a.errflag = h->flags.word(FLAG_OVER);
+    a.G = h->G.p; a.f = e.f; a.virial = e.vtab; a.vatom = e.vatom; a.ncount = h->ncount.p; a.errflag = h->flags.word(FLAG_OVER);
+    return a;
+}
+
+int evaluate_behler(annp_hip_handle *h, const EvalArgs &e, MlpArgs m)
+{
+    int rc;
+    const int inum = e.inum;
+    hipStream_t s = e.s;
+    NiArgs a = ni_args(h, e);
+    a.coef = h->coef.p;
     if (a.npsf > NI_MAXP || a.ntsf > NI_MAXT)
         return fail(h, ANNP_HIP_ESHAPE, "Behler kernels support npsf<=%d ntsf<=%d", NI_MAXP, NI_MAXT);
     const int cap_max = ni_max_cap(true, h->nsf);
@@ -957,6 +968,56 @@ int evaluate_behler(annp_hip_handle *h, const EvalArgs &e, MlpArgs m)
     return 0;
 }
 
+// Will the next Behler evaluation run the one-kernel route?  Asked for (ANNP_HIP_NI_EVAL=fused), a potential it covers (one network),
+// a capacity learned by the passes (the first evaluation, and the one after a capacity error, are theirs: they size the records with
+// one look at the counts and own the error text), and records that fit beside the kernel's pair lists.
+bool ni_fused_next(const annp_hip_handle *h)
+{
+    if (h->descriptor != ANNP_HIP_DESC_BEHLER || !h->ni_fused || !h->d_ni_net || !h->ni_primed) return false;
+    NiArgs a{};
+    a.npsf = h->npsf; a.ntsf = h->ntsf; a.rad_em = h->ni_rad_em;
+    return h->ni_cap <= ni_fused_max_cap(!ni_is_shipped_shape(a, h->ni_shape));
+}
+
+// pair_style annp, Behler descriptor, ANNP_HIP_NI_EVAL=fused: one kernel (+ its fix-up launch) does what evaluate_behler's five launches do.
+// Timing events: [0] and [1] are empty, [2] is the kernel with its fix-up launch (include/annp_hip.h, as for anna_adp).
+int evaluate_behler_fused(annp_hip_handle *h, const EvalArgs &e, const MlpArgs &m)
+{
+    int rc;
+    const int inum = e.inum;
+    hipStream_t s = e.s;
+    NiFusedArgs q{};
+    q.n = ni_args(h, e);
+    NiArgs &a = q.n;
+    const int cap_max = ni_fused_max_cap(!ni_is_shipped_shape(a, h->ni_shape));
+    a.n_cap = std::min(h->ni_cap, cap_max);
+    // a group that outgrew the capacity learned from the evaluation before is queued and taken by the second launch, whose records
+    // hold a whole list row: complete whatever the configuration did meanwhile, as on the passes route
+    const int cap_big = std::min(cap_max, std::max(a.n_cap, round_up(std::max(e.max_numneigh, 8), 8)));
+    const bool fixup = cap_big > a.n_cap && !h->ni_no_fixup;
+    const int ngroups = (inum + NI_GA - 1) / NI_GA;
+    a.ovf_count = h->flags.word(FLAG_NFIX_FORCE); a.ovf_list = nullptr; a.ovf_cap = 0; a.fix = 0; a.skip_above = a.n_cap;
+    if (fixup) {
+        if ((rc = ensure(h, h->ovf, (size_t)ngroups))) return rc;
+        a.ovf_list = h->ovf.p; a.ovf_cap = ngroups;
+    }
+    q.net = h->d_ni_net; q.nnod = h->nnod; q.nlw = h->nl;
+    for (int l = 0; l < MLP_MAXL; l++) q.act[l] = l < h->nl ? h->flagact[l] : 0;
+    q.eatom = m.eatom; q.eng = m.eng; q.nmax_word = h->flags.word(FLAG_NMAX);
+    if ((rc = record_timing(h, 1, s)) || (rc = record_timing(h, 2, s))) return rc;
+    h->cap_last = a.n_cap;
+    if ((rc = wait_pre_force(h, s))) return rc;
+    ni_launch_fused(q, h->ni_shape, e.vir(), s);
+    HIP_TRY(h, hipGetLastError());
+    if (fixup) {
+        NiFusedArgs b = q;
+        b.n.fix = 1; b.n.n_cap = cap_big;
+        ni_launch_fused_fix(b, h->ni_shape, e.vir(), s);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return 0;
+}
+
 int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_x, const int *d_type, const int *d_ilist,
                         const int *d_numneigh, const long long *d_first, const int *d_neigh, int max_numneigh,
                         double *d_f, double *d_eatom, double *d_eng, double *d_virial, double *d_vatom, hipStream_t s)
@@ -1012,6 +1073,7 @@ int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_
     bool ran_sh = false;
     if (h->descriptor == ANNP_HIP_DESC_CHEBYSHEV) rc = evaluate_chebyshev(h, e, m, ran_sh);
     else if (h->descriptor == ANNP_HIP_DESC_ANNA_ADP) rc = evaluate_anna_adp(h, e);
+    else if (ni_fused_next(h)) rc = evaluate_behler_fused(h, e, m);
     else rc = evaluate_behler(h, e, m);
     if (rc) return rc;
 
@@ -1106,6 +1168,7 @@ void read_switches(annp_hip_handle *h)
     if (const char *e = std::getenv("ANNP_HIP_NEIGH_SYNC")) h->nb.lazy = std::atoi(e) == 0;
     if (const char *e = std::getenv("ANNP_HIP_NI_PAIRS")) h->ni_no_pairs = std::atoi(e) == 0;
     if (const char *e = std::getenv("ANNP_HIP_NI_FIXUP")) h->ni_no_fixup = std::atoi(e) == 0;
+    if (const char *e = std::getenv("ANNP_HIP_NI_EVAL")) h->ni_fused = std::strcmp(e, "fused") == 0;      // (anything else: the passes)
     if (const char *e = std::getenv("ANNP_HIP_FE_DESC")) h->fe_desc_pairs = std::strcmp(e, "pairs") == 0;
     if (const char *e = std::getenv("ANNP_HIP_FE_FORCE")) h->fe_force_pairs = std::strcmp(e, "pairs") == 0;
     if (const char *e = std::getenv("ANNP_HIP_VIRIAL")) h->virial_tally = std::strcmp(e, "tally") == 0;
@@ -1156,6 +1219,7 @@ void annp_hip_clear(annp_hip_handle *h)
     if (h->d_sym) (void)hipFree(h->d_sym);
     if (h->d_isym) (void)hipFree(h->d_isym);
     if (h->d_mlp_img) (void)hipFree(h->d_mlp_img);
+    if (h->d_ni_net) (void)hipFree(h->d_ni_net);
     if (h->d_map) (void)hipFree(h->d_map);
     if (h->d_net) (void)hipFree(h->d_net);
     release(h, h->G); release(h, h->coef); release(h, h->x); release(h, h->f); release(h, h->eatom); release(h, h->vatom);
@@ -1406,6 +1470,17 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
             h->img_stride = img.size();
             img_all.insert(img_all.end(), img.begin(), img.end());
         }
+        // the one-kernel Behler route reads its weights from an image of its own (ni_net_build); potentials with several networks stay with the passes
+        if (!cheb && h->ni_fused && ne == 1 && !multi && nsf <= 32 && nnod <= 32 && nl >= 2 && nl <= MLP_MAXL) {
+            const std::vector<int> perm = ni_visit_order(p->cofsymang, p->ntsf);
+            std::vector<int> vis(nsf);
+            for (int k = 0; k < nsf; k++) vis[k] = k < np_ ? k : np_ + perm[k - np_];
+            std::vector<double> net((size_t)ni_net_layout(nsf, nnod, nl).total);
+            ni_net_build(net.data(), p->weight_all, p->bias_all, vis.data(), t.data(), nsf, nnod, nl);
+            INIT_TRY(hipMalloc((void **)&h->d_ni_net, sizeof(double) * net.size()));
+            INIT_TRY(hipMemcpy(h->d_ni_net, net.data(), sizeof(double) * net.size(), hipMemcpyHostToDevice));
+            h->bytes += sizeof(double) * net.size();
+        }
         INIT_TRY(hipMalloc((void **)&h->d_mlp_img, sizeof(double) * img_all.size()));
         INIT_TRY(hipMemcpy(h->d_mlp_img, img_all.data(), sizeof(double) * img_all.size(), hipMemcpyHostToDevice));
         h->bytes += sizeof(double) * img_all.size();
@@ -1505,6 +1580,7 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
         INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_force_fixup<FE_NP, FE_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
         INIT_TRY(hipFuncSetAttribute((const void *)annp_fe_force_fixup<FE_NP, FE_NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
         INIT_TRY(ni_set_lds_attributes());
+        INIT_TRY(ni_fused_set_lds_attributes());
         INIT_TRY(hipFuncSetAttribute((const void *)annp_anna_adp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
         INIT_TRY(hipFuncSetAttribute((const void *)annp_anna_adp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, full));
     }
@@ -1631,7 +1707,7 @@ int annp_hip_eval_path(annp_hip_handle *h)
     if (!h) return ANNP_HIP_EARG;
     DEVICE_GUARD(h);
     if (int rc = h->flags.settle(h, true)) return rc;
-    if (h->descriptor == ANNP_HIP_DESC_BEHLER) return 3;
+    if (h->descriptor == ANNP_HIP_DESC_BEHLER) return ni_fused_next(h) ? 5 : 3;
     if (h->descriptor == ANNP_HIP_DESC_ANNA_ADP) return 4;
     if (h->fe_desc_pairs || h->fe_force_pairs) return 2;
     return h->fe_dense ? 1 : 0;
