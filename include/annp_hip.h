@@ -323,6 +323,37 @@ int annp_hip_last_counts(annp_hip_handle *handle, int *counts, int inum);
  * through it. */
 int annp_hip_last_descriptors(annp_hip_handle *handle, double *rows, int inum);
 
+/* ---- extrapolation guard: is the network asked about neighbourhoods it was trained on? ----------------------------------------
+ * Off by default.  Switched on, every evaluation (whichever kernels it runs, annp_hip_eval_path 0..5) is followed on its stream by one
+ * pass over its descriptor rows that leaves a grade per list entry ii:
+ *     grade(ii) = max_k |G[ii][k] - centre_k| / halfwidth_k        over the nsf features of the potential file
+ * With the potential's own statistics (centre = halfwidth = NULL) -- the arrays the network pass normalises with --
+ *   Behler:    centre = sf_min + (sf_max - sf_min) / 2, halfwidth = (sf_max - sf_min) / 2: grade <= 1 means every symmetry function lies
+ *              inside the range the training set covered (ni/src/pair_annp.cpp:169: g = (G - sf_min) / (sf_max - sf_min));
+ *   Chebyshev: centre = sfnor_avg, halfwidth = 1 / sfnor_scal: the grade is the largest |z-score| (fe_v2/src/pair_annp.cpp:179);
+ *   anna_adp:  the file has no statistics: the caller passes both arrays (otherwise ANNP_HIP_EARG, and the text says so).
+ * An atom "exceeds" when its grade is above the caller's threshold (natural values: 1 for Behler, a few sigma for Chebyshev).  The
+ * library reports and leaves the decision to the caller: no error code, no abort.  The reference has no such guard.
+ * ANNP_HIP_EXTRAPOLATION=<threshold> in the environment at init switches it on with the potential's statistics (for callers
+ * that cannot be changed: annp_gpu_init, the LAMMPS adaptor).  Cost: 9 bytes of device memory per list entry and one streaming kernel.
+ * On the stream given to annp_hip_set_notice: one line when an evaluation first has atoms above the threshold, one when a later one
+ * has none again.
+ *
+ * annp_hip_set_extrapolation   threshold > 0 switches the guard on, <= 0 off (frees its buffers).  centre / halfwidth: [nsf] in the
+ *                              file's feature order, or both NULL.  Waits for the device.
+ * annp_hip_extrapolation_info  the most recent evaluation (a whole annp_hip_compute call counts as one, however its list went to the
+ *                              device).  Waits for that evaluation's flag words only.  n3: entries graded, entries with grade > threshold,
+ *                              (entry, feature) values above it.  *grade_max, *slot, *feature: the largest grade, its list slot (the
+ *                              lowest on ties) and the feature (file order; the lowest on ties) that set it.  Every pointer is nullable.
+ *                              Guard off, or no evaluation since it was switched on: ANNP_HIP_EARG.
+ * annp_hip_last_grades         grades of the most recent evaluation, one per list entry ii (like annp_hip_last_counts), to the host
+ * annp_hip_grades_device       the same array on the device, for callers that stay in HBM: valid until an evaluation on more entries
+ *                              grows it, the guard is switched off or annp_hip_clear (NULL before the first graded evaluation) */
+int annp_hip_set_extrapolation(annp_hip_handle *handle, double threshold, const double *centre, const double *halfwidth);
+int annp_hip_extrapolation_info(annp_hip_handle *handle, long long *n3, double *grade_max, int *slot, int *feature);
+int annp_hip_last_grades(annp_hip_handle *handle, double *grades, int inum);
+int annp_hip_grades_device(annp_hip_handle *handle, const double **d_grades);
+
 /* Replaces annp_gpu_clear: frees everything; the handle is invalid afterwards. NULL ok. */
 void annp_hip_clear(annp_hip_handle *handle);
 

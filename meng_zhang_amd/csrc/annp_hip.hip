@@ -35,6 +35,7 @@
 #include "ni_kernels.hpp"
 #include "ni_fused_kernels.hpp"
 #include "anna_kernels.hpp"
+#include "grade_kernels.hpp"
 #include "step_kernels.hpp"
 #include "replan_kernels.hpp"
 
@@ -115,13 +116,22 @@ enum FlagWord {
     FLAG_NFIX_FORCE = 2,    // length of the force fix-up queue
     FLAG_NFIX_DESC = 3,     // length of the descriptor fix-up queue
     FLAG_SPILLS = 4,        // contributions annp_fe_force_sh's force tables had no bucket for
+    FLAG_XG_ABOVE = 5,      // extrapolation guard (annp_desc_grade): list entries with a grade above the threshold
+    FLAG_XG_VALUES = 6,     // ... and (entry, feature) values above it
 };
+// A pipelined annp_hip_compute is one evaluation to its caller and several to the device (one per run of list chunks): each run's words
+// land in a mirror row of their own, so that what is a SUM over the call (the guard's counters) can be taken over its runs.
+constexpr int ANNP_FLAG_RUNS = 8;
 // the words of one evaluation as they landed on the host, and which evaluation that was (what digest_flags judges them by)
 struct FlagWords {
     int over, mx, nfix_force, nfix_desc;
     unsigned spills;        // (the device adds to an int: above 2^31 it reads negative)
     bool sh;                // the evaluation ran the moment kernels
     int inum;               // ... on that many atoms
+    // extrapolation guard: entries graded (0: the guard was off), entries above the threshold and values above it, summed over the runs
+    // of the call so far; more: further runs of the same call follow (the sums are not final)
+    long long xg_graded, xg_above, xg_values;
+    bool xg_more;
 };
 
 // The flag words and everything that moves them: behind every evaluation a side stream copies its set to the host and clears it again
@@ -129,7 +139,8 @@ struct FlagWords {
 // clearing of ITS set, two evaluations old (begin).  The host looks at a landed copy whenever it next touches the handle (poll).
 struct EvalFlags {
     int *d_flags = nullptr;             // [3][ANNP_NFLAGS]: the sticky word's row and the two sets
-    int *h_flags = nullptr;             // pinned mirror of one evaluation's words, copied back behind every evaluation
+    int *h_flags = nullptr;             // pinned mirror of one evaluation's words, copied back behind every evaluation: [ANNP_FLAG_RUNS] rows, row
+                                        // `run` for the evaluation being issued (0 except in the runs of a pipelined annp_hip_compute)
     int *fw = nullptr;                  // the set of the evaluation being issued (its words 1..7; word 0 is the sticky one of d_flags)
     int par = 0;                        // ... which of the two that is
     hipStream_t side = nullptr;         // the copy and the clearing run beside the caller's stream, not in it (at 128 000 atoms the copy held
@@ -141,6 +152,9 @@ struct EvalFlags {
     bool dirty = false;                 // an evaluation set out and never reached hand_over (an error on the way): begin clears the words in-stream
     bool pending = false;               // a copy into h_flags is in flight or not yet looked at
     bool sh = false; int inum = 0;      // the evaluation the pending words belong to (FlagWords)
+    int run = 0; bool more = false;     // the evaluation being issued is run `run` of its call, and more follow (set_run)
+    long long graded = 0;               // entries the guard has graded in the call so far
+    int landed_run = 0; bool landed_more = false;       // ... as they were when the pending words were handed over
     int sticky_rc = 0;                  // error found in a landed copy, returned by the next call on the handle
     bool reset_err = false;             // the sticky word was seen non-zero: begin clears it
 
@@ -150,15 +164,20 @@ struct EvalFlags {
     void release();
     int begin(annp_hip_handle *h, hipStream_t s);
     int read_now(annp_hip_handle *h, hipStream_t s, FlagWords &w);
-    int hand_over(annp_hip_handle *h, hipStream_t s, bool ran_sh, int ran_inum);
+    int hand_over(annp_hip_handle *h, hipStream_t s, bool ran_sh, int ran_inum, int ran_graded);
+    void set_run(int k, bool more_follow) { run = k; more = more_follow; }
     int settle(annp_hip_handle *h, bool wait);
     int poll(annp_hip_handle *h, bool wait);
 
    private:
     int copy(annp_hip_handle *h, hipStream_t st);
-    FlagWords landed() const
+    // the words in mirror row r (the guard's counters: the sum over rows 0..r)
+    FlagWords landed(int r, bool more_follow) const
     {
-        return FlagWords{h_flags[FLAG_OVER], h_flags[FLAG_NMAX], h_flags[FLAG_NFIX_FORCE], h_flags[FLAG_NFIX_DESC], (unsigned)h_flags[FLAG_SPILLS], sh, inum};
+        const int *w = h_flags + r * ANNP_NFLAGS;
+        long long above = 0, values = 0;
+        for (int k = 0; k <= r; k++) { above += (unsigned)h_flags[k * ANNP_NFLAGS + FLAG_XG_ABOVE]; values += (unsigned)h_flags[k * ANNP_NFLAGS + FLAG_XG_VALUES]; }
+        return FlagWords{w[FLAG_OVER], w[FLAG_NMAX], w[FLAG_NFIX_FORCE], w[FLAG_NFIX_DESC], (unsigned)w[FLAG_SPILLS], sh, inum, graded, above, values, more_follow};
     }
 };
 
@@ -225,6 +244,19 @@ struct annp_hip_handle {
     // ---- flag words of the evaluations
     EvalFlags flags;
 
+    // ---- extrapolation guard (annp_hip_set_extrapolation, grade_kernels.hpp): off unless the caller or ANNP_HIP_EXTRAPOLATION asks for it
+    double xg_threshold = 0.0;          // > 0: every evaluation grades its descriptor rows
+    double xg_env = 0.0;                // ANNP_HIP_EXTRAPOLATION (read_switches), switched on at the end of annp_hip_init
+    std::vector<double> stat_avg, stat_scal;    // the potential's training statistics as annp_hip_init was given them (sfnor_avg, sfnor_scal; none: anna_adp)
+    int xg_slot[ANNP_GPAD] = {0};       // feature k of the file -> its slot in a row of G
+    double *d_xg_stat = nullptr;        // centre | 1 / halfwidth by slot (GradeArgs::stat)
+    DevBuf<double> grade;               // one grade per list entry of the most recent evaluation
+    DevBuf<unsigned char> grade_feat;   // ... and the slot of the feature that set it
+    int xg_base = 0, xg_span = 0;       // a run of a pipelined annp_hip_compute: the list slot its rows start at, and the slots of the whole call
+    long long xg_n3[3] = {0, 0, 0};     // the most recent graded evaluation whose words were looked at: entries, entries above, values above
+    bool xg_have = false;
+    bool xg_said = false;               // the notice stream has been told that atoms are outside the range (digest_flags)
+
     // ---- work buffers of an evaluation
     DevBuf<double> G, coef, mom;        // mom: moments of the neighbourhoods, descriptor pass -> force pass (fe_sh_kernels.hpp)
     DevBuf<double> fscratch;            // forces of one evaluation by themselves, when the global virial is taken as sum x (x) f (annp_fdotr_add)
@@ -274,6 +306,7 @@ struct annp_hip_handle {
     size_t pin_hdr_cap = 0;             // atoms
     static constexpr int kListBufs = 3;
     static constexpr int kListParts = 8;        // runs of chunks a host list is evaluated in while it is uploaded (annp_hip_compute, ago == 0)
+    static_assert(kListParts <= ANNP_FLAG_RUNS, "one mirror row of flag words per run");
     hipEvent_t ev_part[kListParts] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int list_parts = 4;                         // ANNP_HIP_LIST_PARTS (1 = upload first, evaluate afterwards)
     int list_pipe_min = 1 << 16;                // ... for lists of at least that many atoms (ANNP_HIP_LIST_PIPE_MIN)
@@ -496,6 +529,23 @@ void digest_flags(annp_hip_handle *h, const FlagWords &w)
                                       "the affected atoms were skipped", over, h->cap_last);
     }
     if (over > 0) h->flags.reset_err = true;
+    // extrapolation guard: the counters of a whole call (all its runs), and one line when atoms leave the training range or are all back
+    if (w.xg_graded > 0 && !w.xg_more && h->xg_threshold > 0.0) {
+        h->xg_n3[0] = w.xg_graded; h->xg_n3[1] = w.xg_above; h->xg_n3[2] = w.xg_values;
+        h->xg_have = true;
+        const bool outside = w.xg_above > 0;
+        if (outside != h->xg_said) {
+            h->xg_said = outside;
+            if (h->notice) {
+                if (outside)
+                    std::fprintf(h->notice, "annp/hip: %lld of %lld atoms have descriptor values outside the training range (grade above %g; %lld function "
+                                 "values in all): the potential is extrapolating there\n", w.xg_above, w.xg_graded, h->xg_threshold, w.xg_values);
+                else
+                    std::fprintf(h->notice, "annp/hip: no atom has descriptor values outside the training range any more (grade above %g)\n", h->xg_threshold);
+                std::fflush(h->notice);
+            }
+        }
+    }
 }
 
 // ---- EvalFlags ----------------------------------------------------------------------------------------------------------
@@ -507,7 +557,7 @@ hipError_t EvalFlags::allocate()
     fw = d_flags + ANNP_NFLAGS;
     for (hipEvent_t &ev : ev_set)
         if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-    return hipHostMalloc((void **)&h_flags, ANNP_NFLAGS * sizeof(int));
+    return hipHostMalloc((void **)&h_flags, ANNP_FLAG_RUNS * ANNP_NFLAGS * sizeof(int));
 }
 
 void EvalFlags::release()
@@ -541,8 +591,9 @@ int EvalFlags::begin(annp_hip_handle *h, hipStream_t s)
 // the sticky word and the current evaluation's words into the host mirror
 int EvalFlags::copy(annp_hip_handle *h, hipStream_t st)
 {
-    HIP_TRY(h, hipMemcpyAsync(h_flags, d_flags, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(h_flags + 1, fw + 1, (ANNP_NFLAGS - 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+    int *row = h_flags + run * ANNP_NFLAGS;
+    HIP_TRY(h, hipMemcpyAsync(row, d_flags, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipMemcpyAsync(row + 1, fw + 1, (ANNP_NFLAGS - 1) * sizeof(int), hipMemcpyDeviceToHost, st));
     return 0;
 }
 
@@ -556,18 +607,19 @@ int EvalFlags::read_now(annp_hip_handle *h, hipStream_t s, FlagWords &w)
     if (int rc = settle(h, true)) return rc;
     if (int rc = copy(h, s)) return rc;
     HIP_TRY(h, hipStreamSynchronize(s));
-    w = landed();
+    w = landed(run, true);          // (mid-evaluation: the guard has not run yet)
     if (w.over > 0) reset_err = true;
     return 0;
 }
 
 // The evaluation's last kernel is enqueued in s: its words are for whoever looks next (poll).
-int EvalFlags::hand_over(annp_hip_handle *h, hipStream_t s, bool ran_sh, int ran_inum)
+int EvalFlags::hand_over(annp_hip_handle *h, hipStream_t s, bool ran_sh, int ran_inum, int ran_graded)
 {
     HIP_TRY(h, hipEventRecord(ev_tail, s));
     HIP_TRY(h, hipStreamWaitEvent(side, ev_tail, 0));
     // (a copy that is still pending is overwritten, not waited for: of the runs of a pipelined annp_hip_compute only the last one's words
-    // are digested.  Counting such a call as one evaluation for sizing purposes would be changed here and in the two fields below.)
+    // are digested.  Counting such a call as one evaluation for sizing purposes would be changed here and in the two fields below.  The
+    // extrapolation guard does count it as one: every run's copy goes to its own mirror row, and the last run's digest sums them.)
     if (int rc = copy(h, side)) return rc;
     HIP_TRY(h, hipEventRecord(ev_landed, side));
     HIP_TRY(h, hipMemsetAsync(fw + 1, 0, (ANNP_NFLAGS - 1) * sizeof(int), side));
@@ -575,6 +627,8 @@ int EvalFlags::hand_over(annp_hip_handle *h, hipStream_t s, bool ran_sh, int ran
     set_used[par] = true;
     pending = true; dirty = false;
     sh = ran_sh; inum = ran_inum;
+    graded = (run > 0 ? graded : 0) + ran_graded;
+    landed_run = run; landed_more = more;
     return 0;
 }
 
@@ -586,7 +640,7 @@ int EvalFlags::settle(annp_hip_handle *h, bool wait)
     const hipError_t e = wait ? hipEventSynchronize(ev_landed) : hipEventQuery(ev_landed);
     if (e == hipSuccess) {
         pending = false;
-        digest_flags(h, landed());
+        digest_flags(h, landed(landed_run, landed_more));
     } else if (e != hipErrorNotReady) {
         return fail(h, ANNP_HIP_EDEVICE, "flag read-back failed: %s", hipGetErrorString(e));
     }
@@ -1018,6 +1072,60 @@ int evaluate_behler_fused(annp_hip_handle *h, const EvalArgs &e, const MlpArgs &
     return 0;
 }
 
+// ---- extrapolation guard ---------------------------------------------------------------------------------------------------
+// Grades of the evaluation's list entries from the rows it left in G, behind its last pass (every route leaves them there, the fix-up
+// launches included).  A run of a pipelined annp_hip_compute writes its grades at the run's own list slots (xg_base).
+int launch_grade(annp_hip_handle *h, const EvalArgs &e)
+{
+    GradeArgs g{};
+    g.n = e.inum; g.G = h->G.p; g.stat = h->d_xg_stat; g.threshold = h->xg_threshold;
+    g.grade = h->grade.p + h->xg_base; g.feat = h->grade_feat.p + h->xg_base;
+    g.ilist = e.ilist; g.type = e.types; g.active = h->active;
+    g.n_above = h->flags.word(FLAG_XG_ABOVE); g.n_values = h->flags.word(FLAG_XG_VALUES);
+    hipLaunchKernelGGL(annp_desc_grade, dim3(grade_blocks(g.n)), dim3(64 * GRADE_WAVES), 0, e.s, g);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
+void guard_release(annp_hip_handle *h)
+{
+    release(h, h->grade); release(h, h->grade_feat);
+    if (h->d_xg_stat) { (void)hipFree(h->d_xg_stat); h->d_xg_stat = nullptr; h->bytes -= 2 * ANNP_GPAD * sizeof(double); }
+    h->xg_threshold = 0.0;
+    h->xg_have = false; h->xg_said = false;
+}
+
+// Switch the guard on (threshold > 0) or off.  centre / halfwidth: [nsf] in the file's feature order, or both null for the potential's own
+// statistics.  The device is idle and the handle's words are digested when this runs.
+int guard_set(annp_hip_handle *h, double threshold, const double *centre, const double *halfwidth)
+{
+    if (!(threshold > 0.0)) { guard_release(h); return 0; }
+    if (!std::isfinite(threshold) || (centre == nullptr) != (halfwidth == nullptr))
+        return fail(h, ANNP_HIP_EARG, "set_extrapolation: a finite threshold, and centre and halfwidth together or not at all");
+    std::vector<double> stat(2 * ANNP_GPAD, 0.0);       // (a slot no feature sits in: width infinite, its value never counts)
+    for (int k = 0; k < h->nsf; k++) {
+        double c, w;
+        if (centre) { c = centre[k]; w = halfwidth[k]; }
+        else if (h->stat_avg.empty())
+            return fail(h, ANNP_HIP_EARG, "set_extrapolation: a pair_style anna_adp potential file carries no training statistics: "
+                        "pass centre and halfwidth of its %d descriptor values", h->nsf);
+        else if (h->descriptor == ANNP_HIP_DESC_BEHLER) { w = 0.5 * h->stat_scal[k]; c = h->stat_avg[k] + w; }      // [sf_min, sf_max]
+        else { c = h->stat_avg[k]; w = 1.0 / h->stat_scal[k]; }                                                    // average, standard deviation
+        if (!std::isfinite(c) || !(w > 0.0) || !std::isfinite(w))
+            return fail(h, ANNP_HIP_EARG, "set_extrapolation: feature %d has centre %g and halfwidth %g (a finite centre and a positive width are needed)", k, c, w);
+        stat[h->xg_slot[k]] = c;
+        stat[ANNP_GPAD + h->xg_slot[k]] = 1.0 / w;
+    }
+    if (!h->d_xg_stat) {
+        HIP_TRY(h, hipMalloc((void **)&h->d_xg_stat, sizeof(double) * stat.size()));
+        h->bytes += sizeof(double) * stat.size();
+    }
+    HIP_TRY(h, hipMemcpy(h->d_xg_stat, stat.data(), sizeof(double) * stat.size(), hipMemcpyHostToDevice));
+    h->xg_threshold = threshold;
+    h->xg_have = false; h->xg_said = false;
+    return 0;
+}
+
 int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_x, const int *d_type, const int *d_ilist,
                         const int *d_numneigh, const long long *d_first, const int *d_neigh, int max_numneigh,
                         double *d_f, double *d_eatom, double *d_eng, double *d_virial, double *d_vatom, hipStream_t s)
@@ -1048,6 +1156,11 @@ int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_
     // a neighbouring row by zero: they must be numbers, whether the network pass wrote them or not)
     if ((rc = ensure(h, h->coef, (size_t)(inum + SHF_GA) * ANNP_CPAD, true))) return rc;
     if ((rc = ensure(h, h->ncount, (size_t)inum))) return rc;
+    const bool graded = h->xg_threshold > 0.0;
+    if (graded) {           // (a run of a pipelined call: room for the whole call's list slots, so that no later run moves the buffer)
+        const size_t slots = (size_t)std::max(h->xg_span, h->xg_base + inum);
+        if ((rc = ensure(h, h->grade, slots)) || (rc = ensure(h, h->grade_feat, slots))) return rc;
+    }
     if ((rc = h->flags.begin(h, s)) || (rc = record_timing(h, 0, s))) return rc;
 
     EvalArgs e{};
@@ -1088,7 +1201,8 @@ int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_
         hipLaunchKernelGGL(annp_virial_fold, dim3(1), dim3(1024), 0, s, vtab, d_virial);
         HIP_TRY(h, hipGetLastError());
     }
-    if ((rc = h->flags.hand_over(h, s, ran_sh, inum))) return rc;
+    if (graded && (rc = launch_grade(h, e))) return rc;
+    if ((rc = h->flags.hand_over(h, s, ran_sh, inum, graded ? inum : 0))) return rc;
     return record_timing(h, 3, s);
 }
 
@@ -1176,6 +1290,7 @@ void read_switches(annp_hip_handle *h)
     if (const char *e = std::getenv("ANNP_HIP_LIST_PARTS")) h->list_parts = std::max(1, std::min((int)annp_hip_handle::kListParts, std::atoi(e)));
     if (const char *e = std::getenv("ANNP_HIP_LIST_PIPE_MIN")) h->list_pipe_min = std::max(1, std::atoi(e));
     if (const char *e = std::getenv("ANNP_HIP_LIST_CHUNK")) h->list_chunk = std::max<size_t>(1024, std::min<size_t>(annp_hip_handle::kListChunk, (size_t)std::atoll(e)));
+    if (const char *e = std::getenv("ANNP_HIP_EXTRAPOLATION")) h->xg_env = std::atof(e);        // threshold of the extrapolation guard (<= 0: off)
     if (const char *e = std::getenv("ANNP_HIP_SH_CAP")) h->sh_cap = std::min((int)SH_CAP_MAX, std::max((int)SH_CAP_MIN, round_up(std::atoi(e), 16)));
 }
 
@@ -1225,6 +1340,7 @@ void annp_hip_clear(annp_hip_handle *h)
     release(h, h->G); release(h, h->coef); release(h, h->x); release(h, h->f); release(h, h->eatom); release(h, h->vatom);
     release(h, h->type); release(h, h->ilist); release(h, h->numneigh); release(h, h->neigh); release(h, h->ncount); release(h, h->ni_nbr); release(h, h->ni_npair); release(h, h->ni_fix_nbr); release(h, h->ni_pairs); release(h, h->ovf);
     release(h, h->mom); release(h, h->fe_nbrs); release(h, h->ovf_desc); release(h, h->fscratch);
+    guard_release(h);
     release(h, h->rp_flag); release(h, h->rp_cnt); release(h, h->rp_pos); release(h, h->rp_bs);
     if (h->rp_tot) (void)hipFree(h->rp_tot);
     if (h->rp_tot_h) (void)hipHostFree(h->rp_tot_h);
@@ -1358,6 +1474,11 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
         h->bytes += sizeof(int) * mp.size();
     }
     for (int l = 0; l < nl; l++) h->flagact[l] = p->flagact[l];
+    // where feature k of the file sits in a descriptor row (Behler: the file's order; Chebyshev kernels always produce FE_NP radial and
+    // FE_NT angular sums), and the training statistics the file has: what the extrapolation guard grades by
+    for (int k = 0; k < p->nsf && k < ANNP_GPAD; k++)
+        h->xg_slot[k] = (p->descriptor != ANNP_HIP_DESC_BEHLER && k >= p->npsf) ? FE_NP + (k - p->npsf) : k;
+    if (!anna) { h->stat_avg.assign(p->sfnor_avg, p->sfnor_avg + p->nsf); h->stat_scal.assign(p->sfnor_scal, p->sfnor_scal + p->nsf); }
 
     if (anna) {
         // network image for annp_anna_adp: layer 0 with its columns in the device feature layout (FE_NP + FE_NT slots)
@@ -1562,7 +1683,7 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
     INIT_TRY(hipMalloc((void **)&h->d_vslots, sizeof(double) * 8 * ANNP_VSLOTS));
     INIT_TRY(h->flags.allocate());
     INIT_TRY(hipHostMalloc((void **)&h->h_scalars, 8 * sizeof(double)));
-    h->bytes += 8 * sizeof(double) + ANNP_NFLAGS * sizeof(int) + sizeof(double) * 8 * ANNP_VSLOTS;
+    h->bytes += 8 * sizeof(double) + ANNP_FLAG_RUNS * ANNP_NFLAGS * sizeof(int) + sizeof(double) * 8 * ANNP_VSLOTS;
     // kernels may ask for the whole LDS
     {
         const int full = 160 * 1024;
@@ -1591,6 +1712,8 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
             return bail(ANNP_HIP_ENOMEM);
     }
     (void)nall_hint; (void)max_nbors_hint;
+    if (h->xg_env > 0.0)        // ANNP_HIP_EXTRAPOLATION
+        if (const int rcg = guard_set(h, h->xg_env, nullptr, nullptr)) return bail(rcg);
 #undef INIT_TRY
     *handle = h;
     return ANNP_HIP_OK;
@@ -1663,6 +1786,60 @@ int annp_hip_last_descriptors(annp_hip_handle *h, double *rows, int inum)
     DEVICE_GUARD(h);
     HIP_TRY(h, hipDeviceSynchronize());
     HIP_TRY(h, hipMemcpy(rows, h->G.p, sizeof(double) * ANNP_GPAD * (size_t)inum, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- extrapolation guard (include/annp_hip.h) ---------------------------------------------------------------------------------
+int annp_hip_set_extrapolation(annp_hip_handle *h, double threshold, const double *centre, const double *halfwidth)
+{
+    if (!h) return ANNP_HIP_EARG;
+    DEVICE_GUARD(h);
+    HIP_TRY(h, hipDeviceSynchronize());         // evaluations in flight read the table and write the buffers this call replaces
+    if (int rc = h->flags.settle(h, true)) return rc;
+    return guard_set(h, threshold, centre, halfwidth);
+}
+
+int annp_hip_extrapolation_info(annp_hip_handle *h, long long *n3, double *grade_max, int *slot, int *feature)
+{
+    if (!h) return ANNP_HIP_EARG;
+    if (!(h->xg_threshold > 0.0)) return fail(h, ANNP_HIP_EARG, "extrapolation_info: the guard is off (annp_hip_set_extrapolation)");
+    DEVICE_GUARD(h);
+    if (int rc = h->flags.settle(h, true)) return rc;       // the words land behind the evaluation's last kernel: its grades are complete too
+    if (!h->xg_have) return fail(h, ANNP_HIP_EARG, "extrapolation_info: no evaluation since the guard was switched on");
+    for (int k = 0; n3 && k < 3; k++) n3[k] = h->xg_n3[k];
+    if (!grade_max && !slot && !feature) return 0;
+    // the largest grade and where it sits: one pass over the grades on the host, the lowest list slot on ties
+    const size_t n = (size_t)h->xg_n3[0];
+    std::vector<double> g(n);
+    HIP_TRY(h, hipMemcpy(g.data(), h->grade.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+    size_t at = 0;
+    for (size_t k = 1; k < n; k++) if (g[k] > g[at]) at = k;
+    unsigned char fslot = 0;
+    HIP_TRY(h, hipMemcpy(&fslot, h->grade_feat.p + at, 1, hipMemcpyDeviceToHost));
+    int fk = 0;
+    for (int k = 0; k < h->nsf; k++) if (h->xg_slot[k] == (int)fslot) fk = k;
+    if (grade_max) *grade_max = g[at];
+    if (slot) *slot = (int)at;
+    if (feature) *feature = fk;
+    return 0;
+}
+
+int annp_hip_last_grades(annp_hip_handle *h, double *grades, int inum)
+{
+    if (!h) return ANNP_HIP_EARG;
+    if (!(h->xg_threshold > 0.0)) return fail(h, ANNP_HIP_EARG, "last_grades: the guard is off (annp_hip_set_extrapolation)");
+    if (!grades || inum < 0 || (size_t)inum > h->grade.cap) return fail(h, ANNP_HIP_EARG, "last_grades: bad argument");
+    DEVICE_GUARD(h);
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(grades, h->grade.p, sizeof(double) * (size_t)inum, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int annp_hip_grades_device(annp_hip_handle *h, const double **d_grades)
+{
+    if (!h) return ANNP_HIP_EARG;
+    if (!d_grades || !(h->xg_threshold > 0.0)) return fail(h, ANNP_HIP_EARG, "grades_device: the guard is off, or no place for the pointer");
+    *d_grades = h->grade.p;
     return 0;
 }
 
@@ -2438,10 +2615,18 @@ static int host_evaluate_uploading(annp_hip_handle *h, int inum, int nall, const
     // (f goes ahead of the list on the second stream: the first run's force pass waits for it)
     if ((rc = host_begin(h, nall, host_type, eflag, eatom_flag, f, eatom, vatom != nullptr, he))) return rc;
     h->list_valid = false;
+    // (the extrapolation guard counts the call as one evaluation: run k grades list slots [a, b) and its counters land in mirror row k)
+    int run = 0;
+    h->xg_span = inum;
     rc = upload_host_list(h, inum, nall, ilist, numj, firstneigh, h->stream2, h->list_parts, [&](int a, int b, hipEvent_t ev) -> int {
         HIP_TRY(h, hipStreamWaitEvent(h->stream, ev, 0));
+        if (run >= ANNP_FLAG_RUNS) return fail(h, ANNP_HIP_EARG, "annp_hip_compute: more than %d runs of list chunks", ANNP_FLAG_RUNS);     // (never: at most list_parts)
+        h->xg_base = a;
+        h->flags.set_run(run++, b < inum);
         return host_compute(h, b - a, nall, he, h->ilist.p + a, h->numneigh.p, h->first.p, h->neigh.p, h->list_max, vflag && virial, vatom != nullptr);
     });
+    h->xg_base = 0; h->xg_span = 0;
+    h->flags.set_run(0, false);
     drain_pre_force_wait(h);
     if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
     return host_finish(h, inum, nall, eflag, vflag, eatom_flag, he.f_on_device, f, eng_vdwl, eatom, virial, vatom);

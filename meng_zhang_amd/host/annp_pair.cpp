@@ -155,6 +155,27 @@ int PairANNP::compute_n(int eflag, int vflag, int eflag_atom, int ago, int inum,
     return 0;
 }
 
+int PairANNP::set_extrapolation(double threshold, const double *centre, const double *halfwidth)
+{
+    if (!handle_) return fail(ANNP_HIP_EARG, "pair style annp/hip used before init_style");
+    const int rc = annp_hip_set_extrapolation(handle_, threshold, centre, halfwidth);
+    return rc ? fail(rc, annp_hip_last_error(handle_)) : 0;
+}
+
+int PairANNP::extrapolation_info(long long *n3, double *grade_max, int *slot, int *feature)
+{
+    if (!handle_) return fail(ANNP_HIP_EARG, "pair style annp/hip used before init_style");
+    const int rc = annp_hip_extrapolation_info(handle_, n3, grade_max, slot, feature);
+    return rc ? fail(rc, annp_hip_last_error(handle_)) : 0;
+}
+
+int PairANNP::grades(double *out, int inum)
+{
+    if (!handle_) return fail(ANNP_HIP_EARG, "pair style annp/hip used before init_style");
+    const int rc = annp_hip_last_grades(handle_, out, inum);
+    return rc ? fail(rc, annp_hip_last_error(handle_)) : 0;
+}
+
 double PairANNP::memory_usage() const
 {
     double bytes = (double)(map_.size() * sizeof(int) + setflag_.size() * sizeof(int) + cutsq_.size() * sizeof(double));
@@ -209,6 +230,15 @@ int annp_pair_compute_n(annp_pair *p, int eflag, int vflag, int eflag_atom, int 
     return p ? p->impl.compute_n(eflag, vflag, eflag_atom, ago, inum, nall, nghost, x, type, sublo, subhi, cutneigh, f, eng_vdwl, eatom, virial, vatom)
              : ANNP_HIP_EARG;
 }
+int annp_pair_set_extrapolation(annp_pair *p, double threshold, const double *centre, const double *halfwidth)
+{
+    return p ? p->impl.set_extrapolation(threshold, centre, halfwidth) : ANNP_HIP_EARG;
+}
+int annp_pair_extrapolation_info(annp_pair *p, long long *n3, double *grade_max, int *slot, int *feature)
+{
+    return p ? p->impl.extrapolation_info(n3, grade_max, slot, feature) : ANNP_HIP_EARG;
+}
+int annp_pair_grades(annp_pair *p, double *grades, int inum) { return p ? p->impl.grades(grades, inum) : ANNP_HIP_EARG; }
 double annp_pair_memory_usage(const annp_pair *p) { return p ? p->impl.memory_usage() : 0.0; }
 const char *annp_pair_error(const annp_pair *p) { return p ? p->impl.error().c_str() : "null pair"; }
 annp_hip_handle *annp_pair_handle(const annp_pair *p) { return p ? p->impl.handle() : nullptr; }

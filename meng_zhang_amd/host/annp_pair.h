@@ -45,6 +45,12 @@ class PairANNP {
                   const double *x, const int *type, const double *sublo, const double *subhi, double cutneigh,
                   double *f, double *eng_vdwl, double *eatom, double *virial, double *vatom);
 
+    // The extrapolation guard of include/annp_hip.h (after init_style): threshold > 0 on, <= 0 off; centre / halfwidth [nsf] or both
+    // null for the training statistics of the potential file.  extrapolation_info and grades describe the most recent compute().
+    int set_extrapolation(double threshold, const double *centre = nullptr, const double *halfwidth = nullptr);
+    int extrapolation_info(long long *n3, double *grade_max, int *slot, int *feature);
+    int grades(double *out, int inum);
+
     double memory_usage() const;
     double cutmax() const { return cutmax_; }
     const Potential &potential() const { return pot_; }
@@ -95,6 +101,9 @@ int annp_pair_compute(annp_pair *p, int eflag, int vflag, int eflag_atom, int ag
 int annp_pair_compute_n(annp_pair *p, int eflag, int vflag, int eflag_atom, int ago, int inum, int nall, int nghost,
                         const double *x, const int *type, const double *sublo, const double *subhi, double cutneigh,
                         double *f, double *eng_vdwl, double *eatom, double *virial, double *vatom);
+int annp_pair_set_extrapolation(annp_pair *p, double threshold, const double *centre, const double *halfwidth);
+int annp_pair_extrapolation_info(annp_pair *p, long long *n3, double *grade_max, int *slot, int *feature);
+int annp_pair_grades(annp_pair *p, double *grades, int inum);
 double annp_pair_memory_usage(const annp_pair *p);
 const char *annp_pair_error(const annp_pair *p);
 annp_hip_handle *annp_pair_handle(const annp_pair *p);

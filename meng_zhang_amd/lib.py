@@ -11,6 +11,7 @@ ABI_SYMBOLS = [
     "annp_hip_init", "annp_hip_compute", "annp_hip_compute_n", "annp_hip_compute_device",
     "annp_hip_neigh_build_device", "annp_hip_list_cutoff", "annp_hip_list_layout", "annp_hip_neigh_to_host", "annp_hip_sync", "annp_hip_eval_info", "annp_hip_eval_path", "annp_hip_set_notice", "annp_hip_set_timing", "annp_hip_last_timing",
     "annp_hip_timing_stats", "annp_hip_last_counts", "annp_hip_last_descriptors",
+    "annp_hip_set_extrapolation", "annp_hip_extrapolation_info", "annp_hip_last_grades", "annp_hip_grades_device",
     "annp_hip_comm_unique_id", "annp_hip_comm_init", "annp_hip_comm_route", "annp_hip_comm_destroy",
     "annp_hip_replan_exchange", "annp_hip_replan_unpack", "annp_hip_replan_faces", "annp_hip_replan_images", "annp_hip_replan_fold_plan",
     "annp_hip_halo_pack", "annp_hip_halo_unpack_images", "annp_hip_reverse_fold", "annp_hip_verlet_half",
@@ -21,6 +22,7 @@ PAIR_SYMBOLS = [
     "annp_pair_init_style", "annp_pair_init_one", "annp_pair_compute", "annp_pair_compute_n",
     "annp_pair_memory_usage", "annp_pair_error", "annp_pair_handle", "annp_pair_potential_info",
     "annp_pair_potential_layer", "annp_pair_potential_sym", "annp_pair_create_style", "annp_pair_potential_anna",
+    "annp_pair_set_extrapolation", "annp_pair_extrapolation_info", "annp_pair_grades",
 ]
 
 
@@ -80,6 +82,10 @@ def load_library():
     lib.annp_hip_timing_stats.argtypes = [vp, dp, ip]
     lib.annp_hip_last_counts.argtypes = [vp, ip, C.c_int]
     lib.annp_hip_last_descriptors.argtypes = [vp, dp, C.c_int]
+    lib.annp_hip_set_extrapolation.argtypes = [vp, C.c_double, dp, dp]
+    lib.annp_hip_extrapolation_info.argtypes = [vp, lp, dp, ip, ip]
+    lib.annp_hip_last_grades.argtypes = [vp, dp, C.c_int]
+    lib.annp_hip_grades_device.argtypes = [vp, C.POINTER(vp)]
     lib.annp_hip_compute_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.annp_hip_neigh_build_device.argtypes = [vp, C.c_int, C.c_int, vp, C.c_double,
                                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), ip, vp]
@@ -101,6 +107,9 @@ def load_library():
     lib.annp_pair_init_one.restype = C.c_double
     lib.annp_pair_compute.argtypes = [vp] + [C.c_int] * 7 + [dp, ip, ip, ip, ipp, dp, dp, dp, dp, dp]
     lib.annp_pair_compute_n.argtypes = [vp] + [C.c_int] * 7 + [dp, ip, dp, dp, C.c_double, dp, dp, dp, dp, dp]
+    lib.annp_pair_set_extrapolation.argtypes = [vp, C.c_double, dp, dp]
+    lib.annp_pair_extrapolation_info.argtypes = [vp, lp, dp, ip, ip]
+    lib.annp_pair_grades.argtypes = [vp, dp, C.c_int]
     lib.annp_pair_memory_usage.argtypes = [vp]
     lib.annp_pair_memory_usage.restype = C.c_double
     lib.annp_pair_error.argtypes = [vp]

@@ -161,6 +161,35 @@ class PairANNP:
     def memory_usage(self):
         return self._lib.annp_pair_memory_usage(self._p)
 
+    # ---- extrapolation guard (include/annp_hip.h) ------------------------------------
+    def set_extrapolation(self, threshold, centre=None, halfwidth=None):
+        """After init_style().  threshold > 0: every compute() also grades each atom's descriptor against the training range,
+        grade = max_k |G_k - centre_k| / halfwidth_k; <= 0: off.  centre / halfwidth: nsf values each in the file's feature order, or
+        both None for the statistics of the potential file (Behler: grade <= 1 inside [sf_min, sf_max]; Chebyshev: largest |z-score|;
+        anna_adp files have none: both are required)."""
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float64)
+        w = None if halfwidth is None else np.ascontiguousarray(halfwidth, dtype=np.float64)
+        nsf = self.potential()["nsf"]
+        for a in (c, w):
+            if a is not None and a.shape != (nsf,):
+                raise ValueError("centre / halfwidth take %d values (nsf of the potential)" % nsf)
+        self._check(self._lib.annp_pair_set_extrapolation(self._p, float(threshold), _dp(c), _dp(w)))
+
+    def extrapolation_info(self):
+        """The most recent compute(): dict(graded, above, values, grade_max, slot, feature) -- list entries graded, entries with a
+        grade above the threshold, (entry, feature) values above it, the largest grade, its list slot and the feature that set it."""
+        n3 = np.zeros(3, dtype=np.int64)
+        gmax, slot, feat = C.c_double(0.0), C.c_int(0), C.c_int(0)
+        self._check(self._lib.annp_pair_extrapolation_info(self._p, n3.ctypes.data_as(C.POINTER(C.c_longlong)), C.byref(gmax),
+                                                           C.byref(slot), C.byref(feat)))
+        return dict(graded=int(n3[0]), above=int(n3[1]), values=int(n3[2]), grade_max=gmax.value, slot=slot.value, feature=feat.value)
+
+    def grades(self):
+        """Grades of the most recent compute(), one per list entry ii."""
+        g = np.zeros(self.list.inum if self.list is not None else self.atom.nlocal)
+        self._check(self._lib.annp_pair_grades(self._p, _dp(g), g.shape[0]))
+        return g
+
     # ---- access for tests / drivers -----------------------------------------------
     @property
     def handle(self):
