@@ -32,7 +32,8 @@
  *     init codes (fe_v2/lib/lal_annp.h:28-33): -1 bad argument / not initialised,
  *     -3 out of device memory, -4 no usable gfx950 device / HIP runtime failure,
  *     -5 double precision unsupported, -7 neighbour capacity exceeded,
- *     -9 unsupported network / descriptor shape.  annp_hip_last_error() gives text.
+ *     -9 unsupported network / descriptor shape (Behler: more than 64 symmetry functions, 32 radial, 64 angular or 64 nodes per
+ *     layer; Chebyshev: more than 9 radial, 19 angular orders or 32 nodes; the text names the limit).  annp_hip_last_error() gives text.
  *     Nothing throws or exits across this boundary.
  *   - one caller thread per handle; several handles per process are fine.
  */
@@ -291,6 +292,12 @@ int annp_hip_eval_info(annp_hip_handle *handle, int *info4);
  *      atom group in one launch.  The first evaluation on a handle and the one after a capacity error run the passes (3), which size
  *      the records; potentials with several networks and records too long for that kernel's LDS stay at 3.  Its timing events follow
  *      the anna_adp convention: ms4[0] and [1] empty, [2] the kernel with its fix-up launch, [3] the whole evaluation.
+ *   6  Behler G2/G4, the wide kernels (meng_zhang_amd/csrc/ni_wide_kernels.hpp): a potential larger than routes 3 and 5 take -- up to 64
+ *      symmetry functions (32 radial, 64 angular), 64 nodes per hidden layer, any real zeta >= 0, any lambda, any number of distinct eta --
+ *      or any Behler potential when the handle was made under ANNP_HIP_NI_EVAL=wide.  Chosen once, at init, by the potential's shape: a
+ *      potential routes 3 and 5 accept keeps them.  Descriptor and coefficient rows are 64 doubles (annp_hip_descriptor_pitch); records
+ *      for 128 in-range neighbours per atom, no fix-up launch and no learned capacity: an atom with more is skipped and reported as
+ *      ANNP_HIP_ENEIGHCAP like every device-side capacity error.  Timing events as for 3.
  * The change 0 -> 1 is also announced once on the stream given to annp_hip_set_notice (annp_gpu_init passes LAMMPS' screen).
  * So is one more thing a caller would otherwise only see in its timings: atoms in no spatial order.  The force pass collects
  * forces in a table whose buckets hold eight atoms with consecutive indices; a caller that sorts its atoms in space (LAMMPS:
@@ -322,9 +329,15 @@ int annp_hip_last_counts(annp_hip_handle *handle, int *counts, int inum);
  * in [0,9), angular T_0..T_18 in [9,28); Behler: the G2/G4 sums.  A diagnostic: the parity tests compare two descriptor kernels
  * through it. */
 int annp_hip_last_descriptors(annp_hip_handle *handle, double *rows, int inum);
+/* Doubles per descriptor row on this handle: 32, or 64 on a Behler handle that runs the wide kernels (annp_hip_eval_path 6).
+ * annp_hip_last_descriptors keeps its meaning (32 doubles per entry) and returns ANNP_HIP_ESHAPE on a handle whose rows are wider;
+ * annp_hip_last_descriptors_pitched copies rows of `pitch` doubles, which must be the handle's pitch (ANNP_HIP_ESHAPE otherwise).
+ * On a wide handle slot k of a row is function k of the potential file (radial functions first), slots nsf..63 are zero. */
+int annp_hip_descriptor_pitch(const annp_hip_handle *handle);
+int annp_hip_last_descriptors_pitched(annp_hip_handle *handle, double *rows, int inum, int pitch);
 
 /* ---- extrapolation guard: is the network asked about neighbourhoods it was trained on? ----------------------------------------
- * Off by default.  Switched on, every evaluation (whichever kernels it runs, annp_hip_eval_path 0..5) is followed on its stream by one
+ * Off by default.  Switched on, every evaluation (whichever kernels it runs, annp_hip_eval_path 0..6) is followed on its stream by one
  * pass over its descriptor rows that leaves a grade per list entry ii:
  *     grade(ii) = max_k |G[ii][k] - centre_k| / halfwidth_k        over the nsf features of the potential file
  * With the potential's own statistics (centre = halfwidth = NULL) -- the arrays the network pass normalises with --

@@ -34,6 +34,7 @@
 #include "neigh_kernels.hpp"
 #include "ni_kernels.hpp"
 #include "ni_fused_kernels.hpp"
+#include "ni_wide_kernels.hpp"
 #include "anna_kernels.hpp"
 #include "grade_kernels.hpp"
 #include "step_kernels.hpp"
@@ -196,7 +197,8 @@ struct annp_hip_handle {
     int flagact[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // up to max(MLP_MAXL, ANNA_MAXL) weight layers
     static_assert(MLP_MAXL <= 8 && ANNA_MAXL <= 8, "flagact holds 8 layers");
     double e_scale = 0, e_shift = 0, e_atom = 0, cut = 0, cutsq = 0;
-    double *d_norm = nullptr;           // nmul | nsub | nden, ANNP_GPAD each
+    int gpad = ANNP_GPAD, cpad = ANNP_CPAD;     // doubles per row of G and of coef: 32 and 48, the wide Behler route 64 and 64 (NIW_PITCH)
+    double *d_norm = nullptr;           // nmul | nsub | nden, gpad each
     double *d_mlp_img = nullptr;        // network pass: MFMA operand images (weights, biases, coefmat), one per element, mlp_build_image
     size_t img_stride = 0;              // doubles per element image
     bool mlp_attr_done = false;
@@ -216,6 +218,10 @@ struct annp_hip_handle {
     bool ni_no_pairs = false;           // ANNP_HIP_NI_PAIRS=0: the Behler force pass finds its pairs itself (no lists through memory)
     bool ni_fused = false;              // ANNP_HIP_NI_EVAL=fused: descriptor, network and force of a group in one kernel (ni_fused_kernels.hpp) once the capacity is known
     double *d_ni_net = nullptr;         // ... its network image (ni_net_build); null: the potential is not covered (several networks), the passes run
+    bool ni_wide = false;               // the wide route (ni_wide_kernels.hpp, annp_hip_eval_path 6): decided once, at init (behler_route)
+    bool ni_wide_asked = false;         // ANNP_HIP_NI_EVAL=wide: any Behler potential takes it
+    double *d_niw_img = nullptr;        // ... its network images, NIW_IMG doubles per element (niw_build_image)
+    double *d_niw_cmul = nullptr;       // ... [NIW_PITCH] 1 / (sf_max - sf_min): coef_k = cmul_k dE/dGhat_k
     double *d_sym = nullptr;            // function tables (ni_kernels.hpp, "per-function tables")
     int *d_isym = nullptr;
     unsigned long long ni_rad_em = 0;   // NiArgs::rad_em
@@ -248,7 +254,7 @@ struct annp_hip_handle {
     double xg_threshold = 0.0;          // > 0: every evaluation grades its descriptor rows
     double xg_env = 0.0;                // ANNP_HIP_EXTRAPOLATION (read_switches), switched on at the end of annp_hip_init
     std::vector<double> stat_avg, stat_scal;    // the potential's training statistics as annp_hip_init was given them (sfnor_avg, sfnor_scal; none: anna_adp)
-    int xg_slot[ANNP_GPAD] = {0};       // feature k of the file -> its slot in a row of G
+    int xg_slot[NIW_PITCH] = {0};       // feature k of the file -> its slot in a row of G
     double *d_xg_stat = nullptr;        // centre | 1 / halfwidth by slot (GradeArgs::stat)
     DevBuf<double> grade;               // one grade per list entry of the most recent evaluation
     DevBuf<unsigned char> grade_feat;   // ... and the slot of the feature that set it
@@ -512,6 +518,11 @@ void digest_flags(annp_hip_handle *h, const FlagWords &w)
         if (over > 0)
             h->flags.sticky_rc = fail(h, ANNP_HIP_ENEIGHCAP, "an atom has %d in-cutoff neighbours, more than the list-row capacity the "
                                       "evaluation was given (max_numneigh) or than LDS holds; it was skipped", over);
+    } else if (h->ni_wide) {        // fixed records, nothing learned between evaluations
+        h->info[3] = NIW_CAP;
+        if (over > 0)
+            h->flags.sticky_rc = fail(h, ANNP_HIP_ENEIGHCAP, "%d neighbours inside the descriptor cutoff exceed the %d records per atom of the wide Behler "
+                                      "kernels; the affected atoms were skipped", over, (int)NIW_CAP);
     } else if (h->descriptor == ANNP_HIP_DESC_BEHLER) {
         if (over > 0) {         // not an atom that outgrew its records (the fix-up launches take those): more than LDS can hold
             h->ni_cap = round_up(over + 2, 8);
@@ -1027,7 +1038,7 @@ int evaluate_behler(annp_hip_handle *h, const EvalArgs &e, MlpArgs m)
 // one look at the counts and own the error text), and records that fit beside the kernel's pair lists.
 bool ni_fused_next(const annp_hip_handle *h)
 {
-    if (h->descriptor != ANNP_HIP_DESC_BEHLER || !h->ni_fused || !h->d_ni_net || !h->ni_primed) return false;
+    if (h->descriptor != ANNP_HIP_DESC_BEHLER || h->ni_wide || !h->ni_fused || !h->d_ni_net || !h->ni_primed) return false;
     NiArgs a{};
     a.npsf = h->npsf; a.ntsf = h->ntsf; a.rad_em = h->ni_rad_em;
     return h->ni_cap <= ni_fused_max_cap(!ni_is_shipped_shape(a, h->ni_shape));
@@ -1072,6 +1083,47 @@ int evaluate_behler_fused(annp_hip_handle *h, const EvalArgs &e, const MlpArgs &
     return 0;
 }
 
+// pair_style annp, Behler descriptor, wide route (ni_wide_kernels.hpp): descriptor pass -> network pass (one launch per element) -> force
+// pass.  Fixed records of NIW_CAP neighbours per atom: no learned capacity, no fix-up launch, no look at the counts; an atom with more is
+// skipped and reported through the error word like every device-side capacity error.  Timing events as for the passes of route 3.
+int evaluate_behler_wide(annp_hip_handle *h, const EvalArgs &e, const MlpArgs &m)
+{
+    int rc;
+    const int inum = e.inum;
+    hipStream_t s = e.s;
+    NiWideArgs a{};
+    a.inum = inum; a.ilist = e.ilist; a.x = e.x; a.type = e.types; a.active = h->active;
+    a.numneigh = e.numneigh; a.first = e.first; a.neigh = e.neigh;
+    a.npsf = h->npsf; a.ntsf = h->ntsf; a.compat = h->ni_compat;
+    a.rad = h->d_sym; a.ang = h->d_sym + 3 * (size_t)h->npsf;
+    a.rc_rad = h->sym_rad[2]; a.rc_ang = h->sym_ang[3];
+    a.por_rad = ANNP_MY_PI / a.rc_rad; a.por_ang = ANNP_MY_PI / a.rc_ang;
+    a.G = h->G.p; a.coef = h->coef.p; a.f = e.f; a.virial = e.vtab; a.vatom = e.vatom;
+    a.ncount = h->ncount.p; a.errflag = h->flags.word(FLAG_OVER);
+    hipLaunchKernelGGL(annp_niw_desc, dim3(niw_blocks(inum)), dim3(64 * NIW_WAVES), 0, s, a);
+    HIP_TRY(h, hipGetLastError());
+    if ((rc = launch_max_count(h, inum, s)) || (rc = record_timing(h, 1, s))) return rc;
+    MlpWideArgs w{};
+    w.inum = inum; w.ilist = e.ilist; w.nsf = h->nsf; w.nnod = h->nnod; w.nl = h->nl;
+    for (int l = 0; l < MLP_MAXL; l++) w.act[l] = l < h->nl ? h->flagact[l] : 0;
+    w.act_plain = 1;
+    w.nsub = h->d_norm + h->gpad; w.nden = h->d_norm + 2 * h->gpad; w.cmul = h->d_niw_cmul;
+    w.G = h->G.p; w.coef = h->coef.p; w.eatom = m.eatom; w.eng = m.eng;
+    w.type = e.types; w.map = h->d_map; w.active = h->active;
+    for (int el = 0; el < h->nelem; el++) {
+        w.img = h->d_niw_img + (size_t)el * NIW_IMG; w.elem = el;
+        hipLaunchKernelGGL(annp_mlp_wide, dim3(niw_mlp_blocks(inum)), dim3(64 * NIW_WAVES), 0, s, w);
+        HIP_TRY(h, hipGetLastError());
+    }
+    if ((rc = record_timing(h, 2, s))) return rc;
+    h->cap_last = NIW_CAP;
+    if ((rc = wait_pre_force(h, s))) return rc;
+    if (e.vir()) hipLaunchKernelGGL(annp_niw_force<true>, dim3(niw_blocks(inum)), dim3(64 * NIW_WAVES), 0, s, a);
+    else hipLaunchKernelGGL(annp_niw_force<false>, dim3(niw_blocks(inum)), dim3(64 * NIW_WAVES), 0, s, a);
+    HIP_TRY(h, hipGetLastError());
+    return 0;
+}
+
 // ---- extrapolation guard ---------------------------------------------------------------------------------------------------
 // Grades of the evaluation's list entries from the rows it left in G, behind its last pass (every route leaves them there, the fix-up
 // launches included).  A run of a pipelined annp_hip_compute writes its grades at the run's own list slots (xg_base).
@@ -1082,7 +1134,8 @@ int launch_grade(annp_hip_handle *h, const EvalArgs &e)
     g.grade = h->grade.p + h->xg_base; g.feat = h->grade_feat.p + h->xg_base;
     g.ilist = e.ilist; g.type = e.types; g.active = h->active;
     g.n_above = h->flags.word(FLAG_XG_ABOVE); g.n_values = h->flags.word(FLAG_XG_VALUES);
-    hipLaunchKernelGGL(annp_desc_grade, dim3(grade_blocks(g.n)), dim3(64 * GRADE_WAVES), 0, e.s, g);
+    if (h->gpad == GRADE_WIDE_PITCH) hipLaunchKernelGGL(annp_desc_grade_wide, dim3(grade_blocks(g.n)), dim3(64 * GRADE_WAVES), 0, e.s, g);
+    else hipLaunchKernelGGL(annp_desc_grade, dim3(grade_blocks(g.n)), dim3(64 * GRADE_WAVES), 0, e.s, g);
     HIP_TRY(h, hipGetLastError());
     return 0;
 }
@@ -1090,7 +1143,7 @@ int launch_grade(annp_hip_handle *h, const EvalArgs &e)
 void guard_release(annp_hip_handle *h)
 {
     release(h, h->grade); release(h, h->grade_feat);
-    if (h->d_xg_stat) { (void)hipFree(h->d_xg_stat); h->d_xg_stat = nullptr; h->bytes -= 2 * ANNP_GPAD * sizeof(double); }
+    if (h->d_xg_stat) { (void)hipFree(h->d_xg_stat); h->d_xg_stat = nullptr; h->bytes -= 2 * (size_t)h->gpad * sizeof(double); }
     h->xg_threshold = 0.0;
     h->xg_have = false; h->xg_said = false;
 }
@@ -1102,7 +1155,7 @@ int guard_set(annp_hip_handle *h, double threshold, const double *centre, const 
     if (!(threshold > 0.0)) { guard_release(h); return 0; }
     if (!std::isfinite(threshold) || (centre == nullptr) != (halfwidth == nullptr))
         return fail(h, ANNP_HIP_EARG, "set_extrapolation: a finite threshold, and centre and halfwidth together or not at all");
-    std::vector<double> stat(2 * ANNP_GPAD, 0.0);       // (a slot no feature sits in: width infinite, its value never counts)
+    std::vector<double> stat(2 * (size_t)h->gpad, 0.0);       // (a slot no feature sits in: width infinite, its value never counts)
     for (int k = 0; k < h->nsf; k++) {
         double c, w;
         if (centre) { c = centre[k]; w = halfwidth[k]; }
@@ -1114,7 +1167,7 @@ int guard_set(annp_hip_handle *h, double threshold, const double *centre, const 
         if (!std::isfinite(c) || !(w > 0.0) || !std::isfinite(w))
             return fail(h, ANNP_HIP_EARG, "set_extrapolation: feature %d has centre %g and halfwidth %g (a finite centre and a positive width are needed)", k, c, w);
         stat[h->xg_slot[k]] = c;
-        stat[ANNP_GPAD + h->xg_slot[k]] = 1.0 / w;
+        stat[h->gpad + h->xg_slot[k]] = 1.0 / w;
     }
     if (!h->d_xg_stat) {
         HIP_TRY(h, hipMalloc((void **)&h->d_xg_stat, sizeof(double) * stat.size()));
@@ -1151,10 +1204,10 @@ int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_
         if ((rc = ensure(h, h->fscratch, (size_t)nall * 3))) return rc;
         HIP_TRY(h, hipMemsetAsync(h->fscratch.p, 0, sizeof(double) * 3 * (size_t)nall, s));
     }
-    if ((rc = ensure(h, h->G, (size_t)inum * ANNP_GPAD))) return rc;
+    if ((rc = ensure(h, h->G, (size_t)inum * h->gpad))) return rc;
     // (coefficient rows start out as zeros, and there are rows behind the last list entry's: the force pass multiplies a few entries of
     // a neighbouring row by zero: they must be numbers, whether the network pass wrote them or not)
-    if ((rc = ensure(h, h->coef, (size_t)(inum + SHF_GA) * ANNP_CPAD, true))) return rc;
+    if ((rc = ensure(h, h->coef, (size_t)(inum + SHF_GA) * h->cpad, true))) return rc;
     if ((rc = ensure(h, h->ncount, (size_t)inum))) return rc;
     const bool graded = h->xg_threshold > 0.0;
     if (graded) {           // (a run of a pipelined call: room for the whole call's list slots, so that no later run moves the buffer)
@@ -1186,6 +1239,7 @@ int compute_device_impl(annp_hip_handle *h, int inum, int nall, const double *d_
     bool ran_sh = false;
     if (h->descriptor == ANNP_HIP_DESC_CHEBYSHEV) rc = evaluate_chebyshev(h, e, m, ran_sh);
     else if (h->descriptor == ANNP_HIP_DESC_ANNA_ADP) rc = evaluate_anna_adp(h, e);
+    else if (h->ni_wide) rc = evaluate_behler_wide(h, e, m);
     else if (ni_fused_next(h)) rc = evaluate_behler_fused(h, e, m);
     else rc = evaluate_behler(h, e, m);
     if (rc) return rc;
@@ -1282,7 +1336,10 @@ void read_switches(annp_hip_handle *h)
     if (const char *e = std::getenv("ANNP_HIP_NEIGH_SYNC")) h->nb.lazy = std::atoi(e) == 0;
     if (const char *e = std::getenv("ANNP_HIP_NI_PAIRS")) h->ni_no_pairs = std::atoi(e) == 0;
     if (const char *e = std::getenv("ANNP_HIP_NI_FIXUP")) h->ni_no_fixup = std::atoi(e) == 0;
-    if (const char *e = std::getenv("ANNP_HIP_NI_EVAL")) h->ni_fused = std::strcmp(e, "fused") == 0;      // (anything else: the passes)
+    if (const char *e = std::getenv("ANNP_HIP_NI_EVAL")) {      // (anything else: the passes)
+        h->ni_fused = std::strcmp(e, "fused") == 0;
+        h->ni_wide_asked = std::strcmp(e, "wide") == 0;
+    }
     if (const char *e = std::getenv("ANNP_HIP_FE_DESC")) h->fe_desc_pairs = std::strcmp(e, "pairs") == 0;
     if (const char *e = std::getenv("ANNP_HIP_FE_FORCE")) h->fe_force_pairs = std::strcmp(e, "pairs") == 0;
     if (const char *e = std::getenv("ANNP_HIP_VIRIAL")) h->virial_tally = std::strcmp(e, "tally") == 0;
@@ -1335,6 +1392,8 @@ void annp_hip_clear(annp_hip_handle *h)
     if (h->d_isym) (void)hipFree(h->d_isym);
     if (h->d_mlp_img) (void)hipFree(h->d_mlp_img);
     if (h->d_ni_net) (void)hipFree(h->d_ni_net);
+    if (h->d_niw_img) (void)hipFree(h->d_niw_img);
+    if (h->d_niw_cmul) (void)hipFree(h->d_niw_cmul);
     if (h->d_map) (void)hipFree(h->d_map);
     if (h->d_net) (void)hipFree(h->d_net);
     release(h, h->G); release(h, h->coef); release(h, h->x); release(h, h->f); release(h, h->eatom); release(h, h->vatom);
@@ -1371,6 +1430,22 @@ void annp_hip_clear(annp_hip_handle *h)
     delete h;
 }
 
+// Which kernels a Behler potential gets: the one owner of that decision, asked once by annp_hip_init.  The tuned kernels (ni_kernels.hpp,
+// routes 3 and 5) take what they always took; a potential they would refuse for its size, for a zeta that is not an integer in [0, 32) or
+// for more than NI_MAXE distinct eta takes the wide ones (ni_wide_kernels.hpp, route 6), and so does any potential when the handle is made
+// under ANNP_HIP_NI_EVAL=wide.  Returns true for the wide route.
+static bool behler_route_wide(const annp_hip_params *p, bool asked)
+{
+    if (asked || p->nsf > ANNP_GPAD || p->nnod > 32 || p->npsf > NI_MAXP || p->ntsf > NI_MAXT) return true;
+    std::vector<double> etas;
+    for (int m = 0; m < p->ntsf; m++) {
+        const double z = p->cofsymang[4 * m + 2];
+        if (!(z >= 0.0 && z < 32.0 && z == std::floor(z))) return true;
+        if (std::find(etas.begin(), etas.end(), p->cofsymang[4 * m]) == etas.end()) etas.push_back(p->cofsymang[4 * m]);
+    }
+    return (int)etas.size() > NI_MAXE;
+}
+
 // Order in which the Behler kernels visit the angular functions: by (lambda, eta, zeta) -- one squaring ladder per lambda, one exp per
 // pair.  perm[pos] = index of the function in the file's order.
 static std::vector<int> ni_visit_order(const double *ang, int nt)
@@ -1400,6 +1475,14 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
             !p->bias_all)
             return fail(nullptr, ANNP_HIP_ESHAPE, "unsupported anna_adp shape ntl=%d nnod=%d nout=%d nsf=%d (%d+%d) ngp=%d",
                         p->ntl, p->nnod, p->nout, p->nsf, p->npsf, p->ntsf, p->ngp);
+    } else if (p->descriptor == ANNP_HIP_DESC_BEHLER) {         // the wide kernels' limits (ni_wide_kernels.hpp); the tuned ones take a subset (behler_route_wide)
+        if (nl < 2 || nl > MLP_MAXL || p->nsf < 1 || p->nnod < 1 || p->npsf < 0 || p->ntsf < 0 || p->npsf + p->ntsf != p->nsf || !p->flagact ||
+            !p->sfnor_scal || !p->sfnor_avg || !p->weight_all || !p->bias_all)
+            return fail(nullptr, ANNP_HIP_ESHAPE, "unsupported network shape ntl=%d nnod=%d nsf=%d (%d+%d)", p->ntl, p->nnod, p->nsf, p->npsf, p->ntsf);
+        if (p->nsf > NIW_PITCH) return fail(nullptr, ANNP_HIP_ESHAPE, "unsupported descriptor shape: nsf=%d symmetry functions, the Behler kernels take up to %d", p->nsf, (int)NIW_PITCH);
+        if (p->npsf > NIW_MAXP) return fail(nullptr, ANNP_HIP_ESHAPE, "unsupported descriptor shape: npsf=%d radial functions, the Behler kernels take up to %d", p->npsf, (int)NIW_MAXP);
+        if (p->ntsf > NIW_MAXT) return fail(nullptr, ANNP_HIP_ESHAPE, "unsupported descriptor shape: ntsf=%d angular functions, the Behler kernels take up to %d", p->ntsf, (int)NIW_MAXT);
+        if (p->nnod > NIW_MAXNOD) return fail(nullptr, ANNP_HIP_ESHAPE, "unsupported network shape: nnod=%d nodes per layer, the Behler kernels take up to %d", p->nnod, (int)NIW_MAXNOD);
     } else if (nl < 2 || nl > MLP_MAXL || p->nsf < 1 || p->nsf > ANNP_GPAD || p->nnod < 1 || p->nnod > 32 ||
         p->npsf + p->ntsf != p->nsf || !p->flagact || !p->sfnor_scal || !p->sfnor_avg || !p->weight_all || !p->bias_all)
         return fail(nullptr, ANNP_HIP_ESHAPE, "unsupported network shape ntl=%d nnod=%d nsf=%d (%d+%d)", p->ntl, p->nnod, p->nsf, p->npsf, p->ntsf);
@@ -1407,6 +1490,14 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
         return fail(nullptr, ANNP_HIP_ESHAPE, "Chebyshev kernels hold up to %d radial and %d angular orders (got %d %d)", FE_NP, FE_NT, p->npsf, p->ntsf);
     if (p->descriptor == ANNP_HIP_DESC_BEHLER && (!p->cofsymrad || !p->cofsymang))
         return fail(nullptr, ANNP_HIP_EARG, "Behler descriptor needs cofsymrad/cofsymang");
+    if (p->descriptor == ANNP_HIP_DESC_BEHLER) {
+        if (p->npsf < 1 || p->ntsf < 1) return fail(nullptr, ANNP_HIP_ESHAPE, "unsupported descriptor shape: a Behler set needs radial and angular functions (got %d %d)", p->npsf, p->ntsf);
+        for (int m = 0; m < p->ntsf; m++) {
+            const double z = p->cofsymang[4 * m + 2];
+            if (!(z >= 0.0) || !std::isfinite(z))
+                return fail(nullptr, ANNP_HIP_ESHAPE, "angular function %d: zeta = %g, the Behler kernels take a finite zeta >= 0", m, z);
+        }
+    }
     const int ne = std::max(1, p->nelements);
     const int ntypes = std::max(1, p->ntypes);
     if (ntypes > 30) return fail(nullptr, ANNP_HIP_ESHAPE, "more than 30 atom types");
@@ -1466,6 +1557,8 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
     h->e_scale = p->e_scale; h->e_shift = p->e_shift; h->e_atom = p->e_atom; h->cut = p->cut;
     h->cutsq = cutsq_all;
     h->nelem = ne; h->multi = multi; h->active = active;
+    h->ni_wide = p->descriptor == ANNP_HIP_DESC_BEHLER && behler_route_wide(p, h->ni_wide_asked);
+    if (h->ni_wide) { h->gpad = NIW_PITCH; h->cpad = NIW_PITCH; }
     if (multi) {
         std::vector<int> mp((size_t)ntypes + 1, -1);
         for (int t = 1; t <= ntypes; t++) mp[t] = p->map ? p->map[t] : 0;
@@ -1476,7 +1569,7 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
     for (int l = 0; l < nl; l++) h->flagact[l] = p->flagact[l];
     // where feature k of the file sits in a descriptor row (Behler: the file's order; Chebyshev kernels always produce FE_NP radial and
     // FE_NT angular sums), and the training statistics the file has: what the extrapolation guard grades by
-    for (int k = 0; k < p->nsf && k < ANNP_GPAD; k++)
+    for (int k = 0; k < p->nsf && k < NIW_PITCH; k++)
         h->xg_slot[k] = (p->descriptor != ANNP_HIP_DESC_BEHLER && k >= p->npsf) ? FE_NP + (k - p->npsf) : k;
     if (!anna) { h->stat_avg.assign(p->sfnor_avg, p->sfnor_avg + p->nsf); h->stat_scal.assign(p->sfnor_scal, p->sfnor_scal + p->nsf); }
 
@@ -1502,6 +1595,32 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
         INIT_TRY(hipMalloc((void **)&h->d_net, sizeof(double) * img.size()));
         INIT_TRY(hipMemcpy(h->d_net, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice));
         h->bytes += sizeof(double) * img.size();
+    } else if (h->ni_wide) {
+        // the wide Behler route: rows of NIW_PITCH in the file's order, Ghat = (G - sf_min) / (sf_max - sf_min) (ni:168-170),
+        // c_k = dE/dGhat_k / (sf_max - sf_min)_k (ni:186-189), one plain network image per element (niw_build_image)
+        h->nsf_dev = p->nsf;
+        std::vector<double> t(3 * NIW_PITCH, 0.0), cmul(NIW_PITCH, 0.0);
+        for (int k = 0; k < NIW_PITCH; k++) t[k] = t[2 * NIW_PITCH + k] = 1.0;
+        for (int k = 0; k < p->nsf; k++) {
+            t[NIW_PITCH + k] = p->sfnor_avg[k];
+            t[2 * NIW_PITCH + k] = 1.0 / p->sfnor_scal[k];
+            cmul[k] = 1.0 / p->sfnor_scal[k];
+        }
+        std::vector<double> img((size_t)ne * NIW_IMG);
+        for (int e = 0; e < ne; e++) {
+            const double *const *We = p->weight_all + (size_t)e * nl;
+            const double *const *Be = p->bias_all + (size_t)e * nl;
+            for (int l = 0; l < nl; l++)
+                if (!We[l] || !Be[l]) { fail(h, 0, "weight_all / bias_all: element %d layer %d is NULL", e, l); return bail(ANNP_HIP_EARG); }
+            niw_build_image(img.data() + (size_t)e * NIW_IMG, We, Be, p->nsf, p->nnod, nl);
+        }
+        INIT_TRY(hipMalloc((void **)&h->d_norm, sizeof(double) * t.size()));
+        INIT_TRY(hipMemcpy(h->d_norm, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
+        INIT_TRY(hipMalloc((void **)&h->d_niw_cmul, sizeof(double) * cmul.size()));
+        INIT_TRY(hipMemcpy(h->d_niw_cmul, cmul.data(), sizeof(double) * cmul.size(), hipMemcpyHostToDevice));
+        INIT_TRY(hipMalloc((void **)&h->d_niw_img, sizeof(double) * img.size()));
+        INIT_TRY(hipMemcpy(h->d_niw_img, img.data(), sizeof(double) * img.size(), hipMemcpyHostToDevice));
+        h->bytes += sizeof(double) * (t.size() + cmul.size() + img.size());
     } else {   // normalisation of the descriptor and the linear map dE/dZ_0 -> coef
         // Device feature layout.  Behler: the file's order.  Chebyshev: the kernels always produce FE_NP radial
         // and FE_NT angular sums, so feature k of a smaller basis sits in slot k (radial) or FE_NP + (k - npsf)
@@ -1606,7 +1725,19 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
         INIT_TRY(hipMemcpy(h->d_mlp_img, img_all.data(), sizeof(double) * img_all.size(), hipMemcpyHostToDevice));
         h->bytes += sizeof(double) * img_all.size();
     }
-    if (p->descriptor == ANNP_HIP_DESC_BEHLER) {
+    if (h->ni_wide) {
+        // function tables of the wide kernels, the file's order: radial (eta, Rs, Rc) | angular (eta, lambda, zeta, 2^(1-zeta): term_coe, ni:748)
+        h->sym_rad.assign(p->cofsymrad, p->cofsymrad + 3 * p->npsf);
+        h->sym_ang.assign(p->cofsymang, p->cofsymang + 4 * p->ntsf);
+        std::vector<double> t(h->sym_rad);
+        for (int m = 0; m < p->ntsf; m++) {
+            const double *a4 = p->cofsymang + 4 * m;
+            t.push_back(a4[0]); t.push_back(a4[1]); t.push_back(a4[2]); t.push_back(std::pow(2.0, 1.0 - a4[2]));
+        }
+        INIT_TRY(hipMalloc((void **)&h->d_sym, sizeof(double) * t.size()));
+        INIT_TRY(hipMemcpy(h->d_sym, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice));
+        h->bytes += sizeof(double) * t.size();
+    } else if (p->descriptor == ANNP_HIP_DESC_BEHLER) {
         h->sym_rad.assign(p->cofsymrad, p->cofsymrad + 3 * p->npsf);
         h->sym_ang.assign(p->cofsymang, p->cofsymang + 4 * p->ntsf);
         // visit order (lambda, eta, zeta): one squaring ladder per lambda, one exp per pair
@@ -1707,7 +1838,7 @@ int annp_hip_init(annp_hip_handle **handle, const annp_hip_params *p, int device
     }
     // sizing hints, as annp_gpu_init takes them (buffers still grow on demand)
     if (nlocal_hint > 0) {
-        if (ensure(h, h->G, (size_t)nlocal_hint * ANNP_GPAD) || ensure(h, h->coef, (size_t)(nlocal_hint + SHF_GA) * ANNP_CPAD, true) ||
+        if (ensure(h, h->G, (size_t)nlocal_hint * h->gpad) || ensure(h, h->coef, (size_t)(nlocal_hint + SHF_GA) * h->cpad, true) ||
             ensure(h, h->ncount, (size_t)nlocal_hint))
             return bail(ANNP_HIP_ENOMEM);
     }
@@ -1780,14 +1911,20 @@ int annp_hip_last_counts(annp_hip_handle *h, int *counts, int inum)
     return 0;
 }
 
-int annp_hip_last_descriptors(annp_hip_handle *h, double *rows, int inum)
+int annp_hip_descriptor_pitch(const annp_hip_handle *h) { return h ? h->gpad : ANNP_HIP_EARG; }
+
+int annp_hip_last_descriptors_pitched(annp_hip_handle *h, double *rows, int inum, int pitch)
 {
-    if (!h || !rows || inum < 0 || (size_t)inum * ANNP_GPAD > h->G.cap) return h ? fail(h, ANNP_HIP_EARG, "last_descriptors: bad argument") : ANNP_HIP_EARG;
+    if (!h) return ANNP_HIP_EARG;
+    if (pitch != h->gpad) return fail(h, ANNP_HIP_ESHAPE, "last_descriptors: this handle's descriptor rows are %d doubles wide, not %d (annp_hip_descriptor_pitch)", h->gpad, pitch);
+    if (!rows || inum < 0 || (size_t)inum * h->gpad > h->G.cap) return fail(h, ANNP_HIP_EARG, "last_descriptors: bad argument");
     DEVICE_GUARD(h);
     HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemcpy(rows, h->G.p, sizeof(double) * ANNP_GPAD * (size_t)inum, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(rows, h->G.p, sizeof(double) * (size_t)h->gpad * (size_t)inum, hipMemcpyDeviceToHost));
     return 0;
 }
+
+int annp_hip_last_descriptors(annp_hip_handle *h, double *rows, int inum) { return annp_hip_last_descriptors_pitched(h, rows, inum, ANNP_GPAD); }
 
 // ---- extrapolation guard (include/annp_hip.h) ---------------------------------------------------------------------------------
 int annp_hip_set_extrapolation(annp_hip_handle *h, double threshold, const double *centre, const double *halfwidth)
@@ -1884,7 +2021,7 @@ int annp_hip_eval_path(annp_hip_handle *h)
     if (!h) return ANNP_HIP_EARG;
     DEVICE_GUARD(h);
     if (int rc = h->flags.settle(h, true)) return rc;
-    if (h->descriptor == ANNP_HIP_DESC_BEHLER) return ni_fused_next(h) ? 5 : 3;
+    if (h->descriptor == ANNP_HIP_DESC_BEHLER) return h->ni_wide ? 6 : ni_fused_next(h) ? 5 : 3;
     if (h->descriptor == ANNP_HIP_DESC_ANNA_ADP) return 4;
     if (h->fe_desc_pairs || h->fe_force_pairs) return 2;
     return h->fe_dense ? 1 : 0;

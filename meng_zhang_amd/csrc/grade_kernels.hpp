@@ -27,8 +27,8 @@ constexpr int GRADE_MAX_BLOCKS = 2048;      // 256 CUs x 8 workgroups: every wav
 
 struct GradeArgs {
     int n;                          // list entries
-    const double *G;                // [n][ANNP_GPAD] descriptor rows of the evaluation
-    const double *stat;             // centre[ANNP_GPAD] | 1 / halfwidth[ANNP_GPAD] by slot of the row; 0 where no feature of the potential sits
+    const double *G;                // [n][pitch] descriptor rows of the evaluation (pitch: ANNP_GPAD; annp_desc_grade_wide: 64)
+    const double *stat;             // centre[pitch] | 1 / halfwidth[pitch] by slot of the row; 0 where no feature of the potential sits
     double threshold;
     double *grade;                  // [n]
     unsigned char *feat;            // [n] slot of the feature that set the grade
@@ -80,6 +80,61 @@ __global__ __launch_bounds__(64 * GRADE_WAVES) void annp_desc_grade(const GradeA
         grade_row_step<0x112>(v, k);        // row_shr:2
         grade_row_step<0x114>(v, k);        // row_shr:4
         grade_row_step<0x118>(v, k);        // row_shr:8 -> the row's last lane has looked at all sixteen
+        const bool writer = l == 15 && ii < p.n;
+        if (writer) {
+            p.grade[ii] = v;
+            p.feat[ii] = (unsigned char)k;
+        }
+        n_above += __popcll(__ballot(writer && v > thr));
+    }
+    if (lane == 0) { part[2 * wave] = n_above; part[2 * wave + 1] = n_values; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0, b = 0;
+#pragma unroll
+        for (int w = 0; w < GRADE_WAVES; w++) { a += part[2 * w]; b += part[2 * w + 1]; }
+        if (a) atomicAdd(p.n_above, a);
+        if (b) atomicAdd(p.n_values, b);
+    }
+}
+
+// The same pass over rows of 64 doubles (the wide Behler route, ni_wide_kernels.hpp): sixteen lanes still share an entry, each lane now
+// looks at slots 2l, 2l+1 and 32+2l, 32+2l+1 (two double2 loads: a wave's two load instructions read four whole rows of 512 bytes).
+// `stat` is centre[64] | 1 / halfwidth[64].  Same outputs, same counters, same tie rule (the lowest slot).
+constexpr int GRADE_WIDE_PITCH = 64;
+
+__global__ __launch_bounds__(64 * GRADE_WAVES) void annp_desc_grade_wide(const GradeArgs p)
+{
+    __shared__ int part[2 * GRADE_WAVES];
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const int l = lane & 15, row = lane >> 4;
+    const double2 c0 = reinterpret_cast<const double2 *>(p.stat)[l], c1 = reinterpret_cast<const double2 *>(p.stat)[16 + l];
+    const double2 iw0 = reinterpret_cast<const double2 *>(p.stat + GRADE_WIDE_PITCH)[l], iw1 = reinterpret_cast<const double2 *>(p.stat + GRADE_WIDE_PITCH)[16 + l];
+    const double thr = p.threshold;
+    int n_above = 0, n_values = 0;          // wave-uniform
+    for (int base = (blockIdx.x * GRADE_WAVES + wave) * 4; base < p.n; base += gridDim.x * GRADE_PER_BLOCK) {
+        const int ii = base + row;
+        bool live = ii < p.n;
+        if (live && p.type) live = type_mapped(p.active, p.type[p.ilist ? p.ilist[ii] : ii]);
+        double d[4] = {0.0, 0.0, 0.0, 0.0};
+        if (live) {
+            const double2 *g = reinterpret_cast<const double2 *>(p.G + (size_t)ii * GRADE_WIDE_PITCH);
+            const double2 g0 = g[l], g1 = g[16 + l];
+            d[0] = fabs(g0.x - c0.x) * iw0.x; d[1] = fabs(g0.y - c0.y) * iw0.y;
+            d[2] = fabs(g1.x - c1.x) * iw1.x; d[3] = fabs(g1.y - c1.y) * iw1.y;
+        }
+        double v = d[0];
+        int k = 2 * l;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            n_values += __popcll(__ballot(d[q] > thr));
+            const int slot = 2 * l + (q & 1) + 32 * (q >> 1);
+            if (d[q] > v) { v = d[q]; k = slot; }       // (slots ascend with q: the lowest slot stays on ties)
+        }
+        grade_row_step<0x111>(v, k);
+        grade_row_step<0x112>(v, k);
+        grade_row_step<0x114>(v, k);
+        grade_row_step<0x118>(v, k);
         const bool writer = l == 15 && ii < p.n;
         if (writer) {
             p.grade[ii] = v;

@@ -10,7 +10,7 @@ ABI_VERSION = 7          # ANNP_HIP_ABI_VERSION of include/annp_hip.h
 ABI_SYMBOLS = [
     "annp_hip_init", "annp_hip_compute", "annp_hip_compute_n", "annp_hip_compute_device",
     "annp_hip_neigh_build_device", "annp_hip_list_cutoff", "annp_hip_list_layout", "annp_hip_neigh_to_host", "annp_hip_sync", "annp_hip_eval_info", "annp_hip_eval_path", "annp_hip_set_notice", "annp_hip_set_timing", "annp_hip_last_timing",
-    "annp_hip_timing_stats", "annp_hip_last_counts", "annp_hip_last_descriptors",
+    "annp_hip_timing_stats", "annp_hip_last_counts", "annp_hip_last_descriptors", "annp_hip_descriptor_pitch", "annp_hip_last_descriptors_pitched",
     "annp_hip_set_extrapolation", "annp_hip_extrapolation_info", "annp_hip_last_grades", "annp_hip_grades_device",
     "annp_hip_comm_unique_id", "annp_hip_comm_init", "annp_hip_comm_route", "annp_hip_comm_destroy",
     "annp_hip_replan_exchange", "annp_hip_replan_unpack", "annp_hip_replan_faces", "annp_hip_replan_images", "annp_hip_replan_fold_plan",
@@ -82,6 +82,8 @@ def load_library():
     lib.annp_hip_timing_stats.argtypes = [vp, dp, ip]
     lib.annp_hip_last_counts.argtypes = [vp, ip, C.c_int]
     lib.annp_hip_last_descriptors.argtypes = [vp, dp, C.c_int]
+    lib.annp_hip_descriptor_pitch.argtypes = [vp]
+    lib.annp_hip_last_descriptors_pitched.argtypes = [vp, dp, C.c_int, C.c_int]
     lib.annp_hip_set_extrapolation.argtypes = [vp, C.c_double, dp, dp]
     lib.annp_hip_extrapolation_info.argtypes = [vp, lp, dp, ip, ip]
     lib.annp_hip_last_grades.argtypes = [vp, dp, C.c_int]

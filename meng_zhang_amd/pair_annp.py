@@ -190,6 +190,19 @@ class PairANNP:
         self._check(self._lib.annp_pair_grades(self._p, _dp(g), g.shape[0]))
         return g
 
+    def descriptors(self):
+        """Descriptor rows of the most recent compute() as the descriptor pass left them, one per list entry ii: 32 columns, or 64 on a
+        Behler potential that runs the wide kernels (annp_hip_descriptor_pitch)."""
+        n = self.list.inum if self.list is not None else self.atom.nlocal
+        pitch = self._lib.annp_hip_descriptor_pitch(self.handle)
+        if pitch < 0:
+            self._check(pitch)
+        g = np.zeros((n, pitch))
+        rc = self._lib.annp_hip_last_descriptors_pitched(self.handle, _dp(g), n, pitch)
+        if rc != 0:
+            raise RuntimeError("annp_hip_last_descriptors_pitched: code %d: %s" % (rc, self._lib.annp_hip_last_error(self.handle).decode()))
+        return g
+
     # ---- access for tests / drivers -----------------------------------------------
     @property
     def handle(self):

@@ -3,6 +3,7 @@
    python tools/kbench.py fe 80      # bcc Fe, 80^3 cells
    python tools/kbench.py ni 40 40 80  # fcc Ni 40x40x80 cells (512 000 atoms)
    python tools/kbench.py anna 80      # bcc Fe, pair_style anna_adp (list cutoff 5.055 + 2 A)
+   KBENCH_POT=file.ann python tools/kbench.py ni 40 40 80   # another single-element potential file on the same box (ANNP_HIP_NI_EVAL=wide: the wide Behler route)
    KBENCH_VIRIAL=1 python tools/kbench.py fe 80     # with the global virial tallied (vflag_global of an NPT step)
    KBENCH_SHUFFLE=1 python tools/kbench.py fe 40    # atoms in random order (no locality of index: the slow path of the force tables)
    KBENCH_ORDER=lammps python tools/kbench.py fe 80 # atoms in the order LAMMPS' atom_modify sort leaves them (bins of 4.25 A, x fastest, random inside a bin)"""
@@ -39,6 +40,7 @@ def main():
     else:
         x0, box = fcc(*dims, A_NI)
         pot, el = NI_POT, "Ni"
+    pot = os.environ.get("KBENCH_POT") or pot
     xg = perturb(x0, 12345, 0.05)
     if os.environ.get("KBENCH_ORDER") == "lammps":          # what a LAMMPS caller delivers between two sorts
         from meng_zhang_amd.workloads import lammps_sort_order
